@@ -9,8 +9,12 @@ component (N = 10 000 samples/iter), SAMTRON design choices with a fixed number 
 With --gpus N > 1 the components are sharded over the ranks (100 per GPU, weak scaling at a fixed ~10 000 samples per
 iteration: desired samples per component = ceil(100 / N)); one process per GPU, RCCL exchanges (gmmvi_amd/sharded.py).
 
-One JSON line on stdout (rank 0).  Extra objects: "roofline" (dominant kernel, algorithmic FLOPs / HIP-event time),
-"cpu_baseline" (the NumPy oracle = CPU port of the reference algorithm, timed on this host on a bounded sample).
+One JSON line on stdout (rank 0): metric, value, unit, higher_is_better, dtype and ms_per_step of the K timed steps behind
+W warm-up steps; a plain run does nothing else.  --full adds the other measurements: "ms_per_step_steady" (200 further
+iterations at a common age of the run), "roofline" / "kernel_roofline" / "kernels" (a per-kernel HIP-event leg;
+dominant kernel, algorithmic FLOPs / HIP-event time), "cpu_baseline" (the NumPy oracle = CPU port of the reference
+algorithm, timed on this host on a bounded sample) and "matched_elbo" (a fresh device run against the fp64 oracle).
+--dump-outputs DIR writes the mixture the last timed step left behind (log_weights, means, chol_cov) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -354,6 +358,35 @@ def matched_elbo(workload, w):
             "within_tolerance": bool(abs(e_gpu - e_cpu) <= 3 * sg + 1e-2), "oracle": "fp64 oracle run side by side"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20      # array bytes of one --dump-outputs: under 64 MB with the .npy headers
+
+
+def dump_outputs(algo, n_gpus, rank, out_dir):
+    """What a caller of train_iter() receives: the mixture after the last timed step -- log_weights [K], means [K, D],
+    chol_cov [K, D, D] (float32, as the device holds them), in global component order.  Where the three exceed
+    DUMP_BUDGET_BYTES the same fixed, seeded subset of components is written from each, with its indices in
+    component_index.npy (float64).  The sharded paths gather the mixture first (collective: every rank calls this)."""
+    if n_gpus == 1:
+        m = algo.model
+        arrays = {"log_weights": m.log_weights.numpy(), "means": m.means.numpy(), "chol_cov": m.chol_cov.numpy()}
+    else:
+        arrays = dict(zip(("log_weights", "means", "chol_cov"), algo.gather_model()))
+    if rank != 0:
+        return
+    arrays = {name: np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+              for name, a in arrays.items()}
+    k = arrays["log_weights"].shape[0]
+    per_component = sum(a.nbytes for a in arrays.values()) / max(k, 1)
+    if per_component * k > DUMP_BUDGET_BYTES:
+        keep = int(DUMP_BUDGET_BYTES // (per_component + 8))
+        idx = np.sort(np.random.default_rng(0).choice(k, size=keep, replace=False))
+        arrays = {name: a[idx] for name, a in arrays.items()}
+        arrays["component_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 def parse_profile(ctx):
     import ctypes
     buf = ctypes.create_string_buffer(1 << 16)
@@ -371,9 +404,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="ns", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the steady-state window, the per-kernel roofline leg, the CPU baseline and the matched-ELBO check")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the matched ELBO")
     ap.add_argument("--cpu-seconds", type=float, default=80.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the mixture after the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     n_gpus = args.gpus
     if "WORLD_SIZE" not in os.environ and n_gpus > 1:
         # no launcher: start the ranks ourselves, BEFORE anything here touches the GPU
@@ -420,6 +458,40 @@ def main():
     k_span = (None if not adaptive_k else
               f"K {w['k_total']} at the start, {int(algo.model.num_components if n_gpus == 1 else algo.num_components)} after "
               f"{args.warmup + args.steps} iterations")
+    if args.dump_outputs:
+        dump_outputs(algo, n_gpus, rank, args.dump_outputs)
+    k_local = w["k_total"] // n_gpus
+    d, n_tot, k_tot = w["d"], w["n_total"], w["k_total"]
+    result = {
+        "metric": "samples_components_per_sec", "value": pairs_per_step / (elapsed / args.steps),
+        "unit": "samples*components/s", "train_iter_per_sec": args.steps / elapsed,
+        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
+        # the arithmetic of the step's roofline kernel: the fp64 Gram matrix of the MORE estimator, f32 everywhere else
+        "higher_is_better": True, "scaling": "strong" if args.workload in STRONG_WORKLOADS else "weak", "vs_baseline": None,
+        "dtype": "f64" if w["cfg"]["ng_estimator_type"] == "MORE" else "f32", "data": "synthetic",
+        "config": {"workload": f"{args.workload}: {w['kind']} target D={d}, K={k_tot} components "
+                               f"({k_local}/GPU), {w['s']} samples/component, N={n_tot} samples/iter, SAMTRON "
+                               f"({w['cfg']['ng_estimator_type']}, {'adaptive' if w['cfg']['num_component_adapter_type'] == 'adaptive' else 'fixed'} K, reuse ratio "
+                               f"{w['cfg']['sample_selector_config']['ratio_reused_samples_to_desired']:g}, KL trust regions, "
+                               f"improvement-based stepsizes)",
+                   "K": k_tot, "D": d, "N": n_tot, "parallelism": f"component-shard x{n_gpus}",
+                   # which code path issued the iterations: the launches are the same on the first two
+                   "path": ("single C call per iteration (gmmvi_train_iter_samtron)" if getattr(getattr(algo, "_fast_path", None), "eligible", lambda: False)()
+                            else "four C calls per iteration with an all-gather between them (gmmvi_train_iter_sharded_phase)"
+                            if getattr(algo, "_fast", None) is not None
+                            else "module-by-module launches, components partitioned by id (gmmvi_amd/sharded_adaptive.py)"
+                            if adaptive_k and n_gpus > 1
+                            else "module-by-module plug-in calls"),
+                   **({"adaptive": k_span + "; value = mean N K of the timed iterations / time"} if k_span else {})},
+    }
+    if args.full:
+        result.update(full_measurements(args, ctx, algo, w, n_gpus, rank, timed, ms_per_step, elapsed))
+    if rank == 0:
+        print(json.dumps(result))
+
+
+def full_measurements(args, ctx, algo, w, n_gpus, rank, timed, ms_per_step, elapsed):
+    """--full: everything beyond the headline, measured after the timed steps on the same process and mixture."""
     # the same figure at the two ends of a run: over the FIRST iterations of a fresh process (what a short --steps measures: the
     # sample database is still growing, caches are cold) and in the steady state behind them
     first_n = args.warmup + args.steps
@@ -486,26 +558,8 @@ def main():
         if traffic is not None:
             break
     result = {
-        "metric": "samples_components_per_sec", "value": pairs_per_step / (elapsed / args.steps),
-        "unit": "samples*components/s", "train_iter_per_sec": args.steps / elapsed,
-        "n_gpus": n_gpus, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
         "ms_per_step_first": {"iterations": f"{args.warmup + 1}..{args.warmup + args.steps} of a fresh process", "ms": ms_per_step},
         "ms_per_step_steady": {"iterations": f"{max(first_n, 225) + 1}..{max(first_n, 225) + steady_steps}", "ms": steady_ms},
-        "higher_is_better": True, "scaling": "strong" if args.workload in STRONG_WORKLOADS else "weak", "vs_baseline": None, "dtype": "f64" if roof_name == "more_gram" else "f32", "data": "synthetic",
-        "config": {"workload": f"{args.workload}: {w['kind']} target D={d}, K={k_tot} components "
-                               f"({k_local}/GPU), {w['s']} samples/component, N={n_tot} samples/iter, SAMTRON "
-                               f"({w['cfg']['ng_estimator_type']}, {'adaptive' if w['cfg']['num_component_adapter_type'] == 'adaptive' else 'fixed'} K, reuse ratio "
-                               f"{w['cfg']['sample_selector_config']['ratio_reused_samples_to_desired']:g}, KL trust regions, "
-                               f"improvement-based stepsizes)",
-                   "K": k_tot, "D": d, "N": n_tot, "parallelism": f"component-shard x{n_gpus}",
-                   # which code path issued the iterations: the launches are the same on the first two
-                   "path": ("single C call per iteration (gmmvi_train_iter_samtron)" if getattr(getattr(algo, "_fast_path", None), "eligible", lambda: False)()
-                            else "four C calls per iteration with an all-gather between them (gmmvi_train_iter_sharded_phase)"
-                            if getattr(algo, "_fast", None) is not None
-                            else "module-by-module launches, components partitioned by id (gmmvi_amd/sharded_adaptive.py)"
-                            if adaptive_k and n_gpus > 1
-                            else "module-by-module plug-in calls"),
-                   **({"adaptive": k_span + "; value = mean N K of the timed iterations / time"} if k_span else {})},
         "roofline": {"kernel": roof_name, "bound": kernel_bound(roof_name, d), "achieved": achieved, "peak": roof_peak,
                      "unit": "TFLOP/s", "frac": achieved / roof_peak, "traffic": traffic,
                      "avg_us": kernels[roof_name]["avg_us"], "flops_per_launch": fl,
@@ -548,8 +602,7 @@ def main():
                                             f"NumPy/SciPy restatement of the reference's algorithm, the reference's own "
                                             f"arithmetic), median iteration time"}
         result["matched_elbo"] = matched_elbo(args.workload, w)
-    if rank == 0:
-        print(json.dumps(result))
+    return result
 
 
 if __name__ == "__main__":

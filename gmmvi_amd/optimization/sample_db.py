@@ -55,6 +55,10 @@ class _MappedRange:
             if want > (self.reserved + self.chunk - 1) // self.chunk * self.chunk:
                 raise MemoryError(f"sample database: a buffer outgrew its reserved address range of {self.reserved >> 30} GiB "
                                   "(GMMVI_DB_RESERVE_GB)")
+            # mapping changes the device page tables from the host, outside the stream's order: let the queued launches finish
+            # first (among them, at a move into the range, the previous iteration's reads of the buffer being replaced).  Once
+            # per move and per 256 MiB of growth.
+            self.ctx.sync()
             self.ctx.check(self.ctx.lib.gmmvi_vmm_grow(self.ctx.handle, self.base, self.chunk, self.mapped, want))
             self.mapped = want
 

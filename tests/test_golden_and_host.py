@@ -254,6 +254,59 @@ def test_bench_workload_spec_is_host_only():
     assert o.model.means.dtype == np.float32
 
 
+def test_bench_dump_outputs_writes_the_mixture_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: log_weights / means / chol_cov as float32 .npy files; above the byte budget the same seeded subset
+    of components from each array, its indices in component_index.npy.  Host arrays stand in for the device model."""
+    bench = _bench_module()
+
+    class Host:
+        def __init__(self, a):
+            self.a = a
+
+        def numpy(self):
+            return self.a
+
+    rng = np.random.default_rng(5)
+    k, d = 40, 6
+    logw = np.log(rng.dirichlet(np.ones(k))).astype(np.float32)
+    means = rng.normal(size=(k, d)).astype(np.float32)
+    chols = np.tril(rng.normal(size=(k, d, d))).astype(np.float32)
+    model = type("Model", (), {"log_weights": Host(logw), "means": Host(means), "chol_cov": Host(chols)})()
+    algo = type("Algo", (), {"model": model})()
+    bench.dump_outputs(algo, 1, 0, str(tmp_path / "all"))
+    assert sorted(os.listdir(tmp_path / "all")) == ["chol_cov.npy", "log_weights.npy", "means.npy"]
+    for name, a in (("log_weights", logw), ("means", means), ("chol_cov", chols)):
+        got = np.load(tmp_path / "all" / f"{name}.npy")
+        assert got.dtype == np.float32
+        np.testing.assert_array_equal(got, a)
+    bench.dump_outputs(algo, 1, 1, str(tmp_path / "rank1"))               # only rank 0 writes
+    assert not (tmp_path / "rank1").exists()
+
+    per_component = 4 * (1 + d + d * d)
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 10 * per_component + 100)
+    subsets = []
+    for run in ("a", "b"):
+        bench.dump_outputs(algo, 1, 0, str(tmp_path / run))
+        idx = np.load(tmp_path / run / "component_index.npy")
+        assert idx.dtype == np.float64 and len(idx) == 10 and np.all(np.diff(idx) > 0)
+        sel = idx.astype(int)
+        np.testing.assert_array_equal(np.load(tmp_path / run / "means.npy"), means[sel])
+        np.testing.assert_array_equal(np.load(tmp_path / run / "chol_cov.npy"), chols[sel])
+        np.testing.assert_array_equal(np.load(tmp_path / run / "log_weights.npy"), logw[sel])
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= 10 * per_component + 100 + 4 * 128
+        subsets.append(sel)
+    np.testing.assert_array_equal(subsets[0], subsets[1])                 # the sample is fixed, run to run
+
+
+def test_bench_rejects_zero_steps(monkeypatch, capsys):
+    """ms_per_step is the time of one timed step: --steps must name at least one."""
+    bench = _bench_module()
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2 and "--steps" in capsys.readouterr().err
+
+
 def test_random_subset_is_a_uniform_subset_and_the_same_in_oracle_and_product():
     """The candidate draw of the add heuristic (sample_db.py:137-152: shuffle + slice): `random_subset` must return a strictly
     ascending set of distinct indices of the requested size, consume the generator identically in the oracle and in the product

@@ -389,3 +389,32 @@ def test_sample_reuse_with_adaptive_components(fused):
     np.testing.assert_array_equal(g.sample_db.mapping.numpy(), o.sample_db.mapping)
     dev = np.abs(g.model.means.numpy() - o.model.means).max() / max(1.0, np.abs(o.model.means).max())
     assert dev <= 0.1, dev
+
+
+def test_bench_plain_run_prints_the_headline_and_dumps_the_last_step(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: one JSON line with the headline fields and nothing
+    from the --full legs; DIR holds the mixture after W + K iterations, the same as W + K train_iter() calls on the same
+    workload give here."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "tiny", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-4000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line["metric"] == "samples_components_per_sec" and line["unit"] == "samples*components/s"
+    assert line["higher_is_better"] is True and line["dtype"] == "f32" and line["steps"] == 3
+    assert line["ms_per_step"] > 0 and line["value"] > 0
+    assert not {"ms_per_step_steady", "roofline", "kernels", "cpu_baseline", "matched_elbo"} & set(line)
+    sys.path.insert(0, root)
+    import bench
+    algo = bench.make_gmmvi(bench.build("tiny", 1, 0), 1, 0)
+    for _ in range(1 + 3):
+        algo.train_iter()
+    for name, arr in (("log_weights", algo.model.log_weights), ("means", algo.model.means), ("chol_cov", algo.model.chol_cov)):
+        got = np.load(out / f"{name}.npy")
+        assert got.dtype == np.float32
+        np.testing.assert_allclose(got, arr.numpy(), rtol=1e-5, atol=1e-6)

@@ -1,10 +1,10 @@
 #!/bin/bash
 # Developer tool: the bench lines of every workload for profiles/r04_* (run on the GPU box).
 O=gpurun_out/$1; mkdir -p $O
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_ns_driver_cmd.json 2> $O/err.txt
-python3 bench.py > $O/bench_ns.json 2>> $O/err.txt
-for wl in c2 c3 c4 d32 d40 ns_reuse2 c4_adaptive; do python3 bench.py --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2>> $O/err.txt; done
-python3 bench.py --workload c5 --steps 20 --warmup 3 > $O/bench_c5.json 2>> $O/err.txt
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_ns_driver_cmd.json 2> $O/err.txt
+python3 bench.py --full > $O/bench_ns.json 2>> $O/err.txt
+for wl in c2 c3 c4 d32 d40 ns_reuse2 c4_adaptive; do python3 bench.py --full --workload $wl --no-cpu-baseline > $O/bench_$wl.json 2>> $O/err.txt; done
+python3 bench.py --full --workload c5 --steps 20 --warmup 3 > $O/bench_c5.json 2>> $O/err.txt
 python3 - <<PY
 import json, glob
 for f in sorted(glob.glob("$O/bench_*.json")):
