@@ -92,6 +92,7 @@ _PROTOS = {
     "gmmvi_mixture_eval": (_i, [_p, _i, _f, _i, _i, _p, _p, _p, _i, _p, _p, _p]),
     "gmmvi_mixture_eval_dual": (_i, [_p, _i, _f, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
     "gmmvi_target_planar": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p]),
+    "gmmvi_target_logreg": (_i, [_p, _i, _i, _p, _f, _f, _p, _i, _p, _p]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),

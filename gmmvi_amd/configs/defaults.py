@@ -61,4 +61,6 @@ EXPERIMENT_DEFAULTS = {
     "gmm20": _experiment("GMM", {"num_dimensions": 20}, 1, 31.63, 1000., 100),
     "gmm100": _experiment("GMM", {"num_dimensions": 100}, 1, 31.63, 1000., 100),
     "planar_robot_4": _experiment("PlanarRobot4", {}, 300, [1.] + [0.2] * 9, [0.0625] + [0.0025] * 9, 10),
+    "breast_cancer": _experiment("breastCancer", {}, 1, 10., 100., 50),
+    "german_credit": _experiment("GermanCredit", {}, 1, 10., 100., 20),
 }

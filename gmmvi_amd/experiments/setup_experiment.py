@@ -23,7 +23,12 @@ _TARGETS = {
     "STM": ("student_t_mixture", "make_target", True),
     "GMM*": ("gmm", "make_target", True),
     "DIAGGMM*": ("diag_gmm", "make_target", True),
+    "breastCancer": ("logistic_regression", "make_breast_cancer", True),
+    "GermanCredit": ("logistic_regression", "make_german_credit", True),
 }
+
+# the reference's minibatch logistic-regression variants (logistic_regression.py:70-142): out of scope
+_UNSUPPORTED = ("breastCancer_mb", "GermanCredit_mb")
 
 
 def _lookup_target(experiment):
@@ -38,12 +43,17 @@ def _lookup_target(experiment):
 
 
 def get_target_lnpdf(experiment, environment_config, seed):
-    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*; the reference's other benchmark posteriors (logistic
-    regression, BNN, Talos) plug in as ``config['target_fn']`` through the LNPDF interface."""
+    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit (``environment_config``
+    may name the ``dataset_dir``); the reference's other benchmark posteriors (the minibatch logistic regressions, BNN,
+    Talos) plug in as ``config['target_fn']`` through the LNPDF interface."""
+    if experiment in _UNSUPPORTED:
+        raise ValueError(f"get_target_lnpdf(): the minibatch variant {experiment} is not supported by this build (the full-data "
+                         f"posterior {experiment[:-3]} is); pass such a target as config['target_fn']")
     entry = _lookup_target(experiment)
     if entry is None:
         raise ValueError(f"get_target_lnpdf() was called with unknown experiment name: {experiment} "
-                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*; pass other targets as config['target_fn'])")
+                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit; pass other targets "
+                         f"as config['target_fn'])")
     module_name, factory_name, takes_config = entry
     module = importlib.import_module(f"{__package__}.target_distributions.{module_name}")
     factory = getattr(module, factory_name)

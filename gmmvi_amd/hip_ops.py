@@ -92,6 +92,19 @@ def target_planar(ctx, prior_std, goals, likelihood_std, x, want_grad=True):
     return lp, grad
 
 
+def target_logreg(ctx, A, prior_mean, prior_std, x, want_grad=True):
+    """Logistic-regression posterior (csrc/logreg.hip).  A: [M, D] signed data matrix diag(s) X~.  -> (lp [n], grad [n, D])."""
+    m, d = A.shape
+    n = x.shape[0]
+    _req(A, (m, d), name="A"); _req(x, (n, d), name="x")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_logreg(ctx.handle, d, m, A.ptr, float(prior_mean), float(prior_std), x.ptr, n, lp.ptr,
+                                              None if grad is None else grad.ptr))
+    return lp, grad
+
+
 def sample_components(ctx, means, chols, offsets, n, seed=0, first_index=0, stream_id=0, eps=None):
     """offsets: DeviceArray int32 [K+1] prefix sums with offsets[K] == n.  -> (x [n,D], mapping [n] int32)."""
     k, d = means.shape

@@ -49,6 +49,7 @@ class SamtronPlan(C.Structure):
         ("component_stepsize_mode", _i), ("cs_min", _f), ("cs_max", _f), ("cs_inc", _f), ("cs_dec", _f),
         ("weight_stepsize_mode", _i), ("ws_min", _f), ("ws_max", _f), ("ws_inc", _f), ("ws_dec", _f),
         ("weight_update_mode", _i), ("stein_flags", _i), ("presample_next", _i), ("presampled", _i), ("phase", _i),
+        ("logreg_A", _p), ("logreg_M", _i), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
     ]
 
 
@@ -208,6 +209,8 @@ class SamtronFastPath:
         p.target_packed, p.target_logw = tgt.get("packed"), tgt.get("logw")
         p.planar_prior_std, p.planar_goals = tgt.get("prior_std"), tgt.get("goals")
         p.planar_goals_count, p.planar_likelihood_std = tgt.get("G", 0), tgt.get("lik_std", 0.0)
+        p.logreg_A, p.logreg_M = tgt.get("A"), tgt.get("M", 0)
+        p.logreg_prior_mean, p.logreg_prior_std = tgt.get("lr_prior_mean", 0.0), tgt.get("lr_prior_std", 0.0)
         p.means, p.chols, p.logw = model.means.ptr, model.chol_cov.ptr, model.log_weights.ptr
         p.packed, p.packed_new = packed_cur.ptr, packed_new.ptr
         p.stepsizes, p.last_eta, p.l2 = m.stepsizes.ptr, m.last_log_etas.ptr, m.l2_regularizers.ptr

@@ -55,6 +55,7 @@ class ShardedPlan(_C.Structure):
         ("component_stepsize_mode", _i), ("cs_min", _f), ("cs_max", _f), ("cs_inc", _f), ("cs_dec", _f),
         ("weight_stepsize_mode", _i), ("ws_min", _f), ("ws_max", _f), ("ws_inc", _f), ("ws_dec", _f),
         ("stein_flags", _i), ("presample_next", _i), ("presampled", _i), ("scratch", _p),
+        ("logreg_A", _p), ("logreg_M", _i), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
     ]
 
 
@@ -363,6 +364,8 @@ class ShardedGMMVI:
         p.target_packed, p.target_logw = t.get("packed"), t.get("logw")
         p.planar_prior_std, p.planar_goals = t.get("prior_std"), t.get("goals")
         p.planar_goals_count, p.planar_likelihood_std = t.get("G", 0), t.get("lik_std", 0.0)
+        p.logreg_A, p.logreg_M = t.get("A"), t.get("M", 0)
+        p.logreg_prior_mean, p.logreg_prior_std = t.get("lr_prior_mean", 0.0), t.get("lr_prior_std", 0.0)
         p.e1, p.e2, p.e3 = f.e1.ptr, f.e2.ptr, f.e3.ptr
         p.x_all, p.tlp_all, p.tgrad_all = f.x_all.ptr, f.tlp_all.ptr, f.tgrad_all.ptr
         p.E_all, p.reward_all = f.E_all.ptr, f.reward_all.ptr

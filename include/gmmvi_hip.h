@@ -187,6 +187,14 @@ int gmmvi_mixture_eval_dual(gmmvi_ctx* ctx, int family, float nu, int K, int D, 
 int gmmvi_target_planar(gmmvi_ctx* ctx, int D, const float* prior_std_dev, int G, const float* goals_dev,
                         float likelihood_std, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev);
 
+/* Bayesian logistic regression (target_distributions/logistic_regression.py:20-67) and its analytic gradient.
+ * A_dev[M,D] = diag(s) X~ (standardised features behind a bias column, s_m = -1 for label 1, +1 for label 0):
+ *   lp[n]   = sum_m log sigmoid(a_m . w_n) + sum_d log N(w_nd; prior_mean, prior_std^2)
+ *   grad[n] = sum_m sigmoid(-a_m . w_n) a_m - (w_n - prior_mean) / prior_std^2
+ * W_dev[N,D]; grad_out_dev may be NULL.  1 <= D <= GMMVI_MAX_DIM_BLOCKED, M >= 1. */
+int gmmvi_target_logreg(gmmvi_ctx* ctx, int D, int M, const float* A_dev, float prior_mean, float prior_std,
+                        const float* W_dev, int N, float* lp_out_dev, float* grad_out_dev);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
@@ -293,7 +301,8 @@ int gmmvi_weight_stepsize_improvement(gmmvi_ctx* ctx, int K, const float* logw_d
  * n_old == 0 and bg_packed == NULL the background components are the model's own (one sweep for both). */
 typedef struct gmmvi_samtron_plan {
     int32_t K, D, N;                      /* components, dimension, samples of this iteration (sum of the counts) */
-    int32_t target_kind;                  /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot */
+    int32_t target_kind;                  /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot, 2: logistic regression;
+                                           * any other value: GMMVI_ERR_ARG */
     int32_t target_family, target_K;      /* enum gmmvi_family, number of target components */
     float target_nu;
     const float* target_packed;           /* [target_K, stride] */
@@ -350,6 +359,10 @@ typedef struct gmmvi_samtron_plan {
      * updated components but not the weights: with sample reuse the effective sample sizes of the NEXT iteration's window
      * (sample_selector.py:140-202), read back asynchronously, so that the next iteration starts without waiting for them. */
     int32_t phase;
+    /* target_kind 2 (gmmvi_target_logreg): the signed data matrix [logreg_M, D], the isotropic normal prior */
+    const float* logreg_A;
+    int32_t logreg_M;
+    float logreg_prior_mean, logreg_prior_std;
 } gmmvi_samtron_plan;
 int gmmvi_train_iter_samtron(gmmvi_ctx* ctx, const gmmvi_samtron_plan* plan);
 
@@ -408,6 +421,10 @@ typedef struct gmmvi_sharded_plan {
     /* scratch that lives across the four phases (component log densities, merged mixture arrays): caller-owned so that
      * several plans can take turns on one context; at least gmmvi_sharded_scratch_floats(K, D, N) floats */
     float* scratch;
+    /* target_kind 2: as in gmmvi_samtron_plan */
+    const float* logreg_A;
+    int32_t logreg_M;
+    float logreg_prior_mean, logreg_prior_std;
 } gmmvi_sharded_plan;
 size_t gmmvi_sharded_scratch_floats(int K, int D, int N);
 int gmmvi_train_iter_sharded_phase(gmmvi_ctx* ctx, const gmmvi_sharded_plan* plan, int phase /* 1..4 */);
