@@ -48,6 +48,7 @@ _i = C.c_int
 _f = C.c_float
 _sz = C.c_size_t
 _u64 = C.c_uint64
+_u32 = C.c_uint32
 
 _PROTOS = {
     "gmmvi_device_count": (_i, []),
@@ -93,6 +94,8 @@ _PROTOS = {
     "gmmvi_mixture_eval_dual": (_i, [_p, _i, _f, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
     "gmmvi_target_planar": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p]),
     "gmmvi_target_logreg": (_i, [_p, _i, _i, _p, _f, _f, _p, _i, _p, _p]),
+    "gmmvi_target_bnn": (_i, [_p, _i, _i, _i, _i, _p, _p, _u64, _u32, _i, _f, _f, _p, _i, _p, _p]),
+    "gmmvi_bnn_predict": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),

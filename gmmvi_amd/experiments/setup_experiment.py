@@ -16,7 +16,11 @@ from ..models.gmm_wrapper import GmmWrapper
 
 _MAX_REWARD_HISTORY = 10000        # setup_experiment.py:40-41
 
-# experiment name (exact, or prefix when the key ends with "*") -> (module below target_distributions, factory, takes the config)
+# the factory takes the environment config and the run seed as ``dataset_seed`` (setup_experiment.py:77-79 upstream)
+CONFIG_AND_SEED = "config+seed"
+
+# experiment name (exact, or prefix when the key ends with "*") -> (module below target_distributions, factory, takes the
+# config: True, False or CONFIG_AND_SEED)
 _TARGETS = {
     "PlanarRobot4": ("planar_robot", "make_four_goal", False),
     "PlanarRobot1": ("planar_robot", "make_single_goal", False),
@@ -25,6 +29,7 @@ _TARGETS = {
     "DIAGGMM*": ("diag_gmm", "make_target", True),
     "breastCancer": ("logistic_regression", "make_breast_cancer", True),
     "GermanCredit": ("logistic_regression", "make_german_credit", True),
+    "WINE*": ("bnn", "make_WINE_target", CONFIG_AND_SEED),
 }
 
 # the reference's minibatch logistic-regression variants (logistic_regression.py:70-142): out of scope
@@ -43,20 +48,23 @@ def _lookup_target(experiment):
 
 
 def get_target_lnpdf(experiment, environment_config, seed):
-    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit (``environment_config``
-    may name the ``dataset_dir``); the reference's other benchmark posteriors (the minibatch logistic regressions, BNN,
-    Talos) plug in as ``config['target_fn']`` through the LNPDF interface."""
+    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit, WINE* (``environment_config``
+    may name the ``dataset_dir``; WINE takes ``seed`` as its dataset seed and as the seed of its minibatch stream); the
+    reference's other benchmark posteriors (the minibatch logistic regressions, MNIST, Talos) plug in as
+    ``config['target_fn']`` through the LNPDF interface."""
     if experiment in _UNSUPPORTED:
         raise ValueError(f"get_target_lnpdf(): the minibatch variant {experiment} is not supported by this build (the full-data "
                          f"posterior {experiment[:-3]} is); pass such a target as config['target_fn']")
     entry = _lookup_target(experiment)
     if entry is None:
         raise ValueError(f"get_target_lnpdf() was called with unknown experiment name: {experiment} "
-                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit; pass other targets "
-                         f"as config['target_fn'])")
+                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit, WINE*; pass other "
+                         f"targets as config['target_fn'])")
     module_name, factory_name, takes_config = entry
     module = importlib.import_module(f"{__package__}.target_distributions.{module_name}")
     factory = getattr(module, factory_name)
+    if takes_config == CONFIG_AND_SEED:
+        return factory(dataset_seed=seed, **environment_config)
     return factory(**environment_config) if takes_config else factory()
 
 

@@ -1,0 +1,223 @@
+"""Bayesian neural network for regression on the wine-quality data (reference:
+src/gmmvi/experiments/target_distributions/bnn.py:59-311,385-448; configs/experiment_configs/wine.yml).
+
+The posterior is a small MLP, features -> H1 -> H2 -> 1 with sigmoid, sigmoid and linear layers, under an MSE likelihood
+on a minibatch per sample and a zero-mean isotropic normal prior without its constant (bnn.py:205-240):
+    log p(w) = s (-T mean_m (y_m - f(x_m; w))^2 - 0.5 sum_d w_d^2 / sd^2)
+with T the size of the training set and s the likelihood scaling.  The parameter vector is the reference's layout
+(bnn.py:110-128,151-166): per layer the weights [in, out] row-major, then the biases; D = 177 for WINE.  The device
+evaluates it with the analytic gradient (csrc/bnn.hip); the reference uses GradientTape.
+
+Minibatches.  Upstream draws sample i's batch from a freshly reshuffled tf.data stream on every call; TensorFlow's RNG
+cannot be reproduced, so this build defines its own stream, keyed by the target's ``seed`` and a call
+counter c (+1 after every ``log_density`` / ``log_density_and_grad`` call with at least one sample): row j of sample n's
+batch has stream position p = n B + j, epoch e = p div T, rank r = p mod T, and its data row is pi_{seed,c,e}(r), a
+balanced 4-round Feistel network on 2h bits (h = ceil(ceil(log2 T) / 2)) with cycle walking, round i mapping
+(L, R) -> (R, L xor (F_i(R) & (2^h - 1))), F_i(R) = word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter
+(R | i << 24, e, c, 3).  Every epoch visits every row once.  ``minibatch_rows`` restates it in NumPy.
+
+The datasets do not ship with the package: ``dataset_dir`` (``environment_config["dataset_dir"]``), else the
+``GMMVI_DATASET_DIR`` environment variable, names a directory laid out like upstream's ``datasets/`` folder:
+``wine/wine_seed_{0..9}.npz``.
+"""
+import os
+
+import numpy as np
+
+from ... import hip_ops
+from ...device import get_context
+from .lnpdf import LNPDF
+
+DATASET_DIR_ENV = "GMMVI_DATASET_DIR"
+STREAM_MINIBATCH = 3                 # stream ids 0-2: component normals, categorical draws, mixture normals
+MAX_FEATURES, MAX_HIDDEN = 32, 16    # what csrc/bnn.hip supports
+WINE_FILE = os.path.join("wine", "wine_seed_{}.npz")
+WINE_ARRAYS = ("features_train", "labels_train", "features_test", "labels_test", "features_vali", "labels_vali")
+
+_M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
+_W0, _W1 = 0x9E3779B9, 0xBB67AE85
+_MASK32 = np.uint64(0xFFFFFFFF)
+
+
+def _philox_word0(c0, c1, c2, c3, seed):
+    """Word 0 of Philox4x32-10 (csrc/philox.h) for uint64 arrays holding 32-bit counter words."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    k0, k1 = seed & 0xFFFFFFFF, seed >> 32
+    for _ in range(10):
+        p0, p1 = _M0 * c0, _M1 * c2
+        c0, c1, c2, c3 = ((p1 >> np.uint64(32)) ^ c1 ^ np.uint64(k0), p1 & _MASK32,
+                          (p0 >> np.uint64(32)) ^ c3 ^ np.uint64(k1), p0 & _MASK32)
+        k0, k1 = (k0 + _W0) & 0xFFFFFFFF, (k1 + _W1) & 0xFFFFFFFF
+    return c0
+
+
+def feistel_half_bits(num_data):
+    """h = ceil(ceil(log2 T) / 2): the network permutes [0, 2^(2h)) >= [0, T)."""
+    bits = int(num_data - 1).bit_length() if num_data > 1 else 0
+    return (bits + 1) // 2
+
+
+def permute_rows(seed, call, epoch, rank, num_data):
+    """pi_{seed,call,epoch}(rank) for int arrays epoch, rank (rank < num_data) -> int64 rows."""
+    h = feistel_half_bits(num_data)
+    mask = np.uint64((1 << h) - 1)
+    x = np.asarray(rank, np.uint64).copy()
+    e = np.broadcast_to(np.asarray(epoch, np.uint64), x.shape).copy()
+    c = np.uint64(int(call) & 0xFFFFFFFF)
+    todo = np.arange(x.size)
+    x, e = x.reshape(-1), e.reshape(-1)
+    xt, et = x, e
+    while todo.size:
+        L, R = xt >> np.uint64(h), xt & mask
+        for i in range(4):
+            f = _philox_word0(R | np.uint64(i << 24), et, np.full_like(R, c), np.full_like(R, STREAM_MINIBATCH), seed)
+            L, R = R, L ^ (f & mask)
+        xt = (L << np.uint64(h)) | R
+        x[todo] = xt
+        walk = xt >= np.uint64(num_data)                       # cycle walking: apply the whole network again
+        todo, xt, et = todo[walk], xt[walk], et[walk]
+    return x.reshape(np.shape(rank)).astype(np.int64)
+
+
+def minibatch_rows(seed, call, n, batch_size, num_data):
+    """The data rows of the n minibatches of call ``call``: int64 [n, batch_size] (row j of sample i: stream position
+    i * batch_size + j)."""
+    p = np.arange(int(n) * int(batch_size), dtype=np.int64)
+    return permute_rows(seed, call, p // num_data, p % num_data, num_data).reshape(int(n), int(batch_size))
+
+
+def num_parameters(num_features, hidden_units):
+    d, last = 0, int(num_features)
+    for width in list(hidden_units) + [1]:
+        d += last * int(width) + int(width)
+        last = int(width)
+    return d
+
+
+class BNNRegression(LNPDF):
+    """Posterior of a features -> H1 -> H2 -> 1 sigmoid network with an MSE likelihood on minibatches of
+    ``batch_size`` rows and a zero-mean normal prior of standard deviation ``prior_std`` (bnn.py:59-240).
+
+    ``features`` [T, F] and ``labels`` [T] are the training set; ``eval_sets`` maps "test" / "vali" to (features, labels)
+    pairs for ``expensive_metrics``.  ``seed`` keys the minibatch stream; ``call_count`` is the number of evaluations so
+    far (the stream's call counter)."""
+
+    def __init__(self, features, labels, hidden_units=(8, 8), likelihood_scaling=1., prior_std=1., batch_size=128,
+                 seed=0, eval_sets=None):
+        super().__init__(use_log_density_and_grad=True)
+        X = np.asarray(features, np.float32)
+        y = np.asarray(labels, np.float32)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError(f"features must be [T, F] and labels [T], got {X.shape} and {y.shape}")
+        hidden_units = tuple(int(h) for h in hidden_units)
+        if len(hidden_units) != 2:
+            raise ValueError(f"hidden_units must name two hidden layers, got {hidden_units}")
+        if not 1 <= X.shape[1] <= MAX_FEATURES:
+            raise ValueError(f"the network takes 1 to {MAX_FEATURES} features, got {X.shape[1]}")
+        if not all(1 <= h <= MAX_HIDDEN for h in hidden_units):
+            raise ValueError(f"hidden layers must have 1 to {MAX_HIDDEN} units, got {hidden_units}")
+        if not 1 <= int(batch_size) <= X.shape[0]:
+            raise ValueError(f"batch_size must lie in [1, {X.shape[0]}] (the training-set size), got {batch_size}")
+        if not prior_std > 0:
+            raise ValueError("prior_std must be positive")
+        self.features, self.labels = X, y
+        self.hidden_units = hidden_units
+        self.likelihood_scaling, self.prior_std = float(likelihood_scaling), float(prior_std)
+        self.batch_size, self.seed = int(batch_size), int(seed)
+        self.eval_sets = {k: (np.asarray(f, np.float32), np.asarray(l, np.float32))
+                          for k, (f, l) in (eval_sets or {}).items()}
+        self._call = 0
+        self.ctx = get_context()
+        self._X_dev, self._y_dev = self.ctx.asarray(X), self.ctx.asarray(y)
+
+    @property
+    def call_count(self):
+        return self._call
+
+    @property
+    def train_size(self):
+        return int(self.features.shape[0])
+
+    def get_num_dimensions(self):
+        return num_parameters(self.features.shape[1], self.hidden_units)
+
+    def _evaluate(self, x, want_grad):
+        x = self.ctx.asarray(x)
+        lp, grad = hip_ops.target_bnn(self.ctx, self._X_dev, self._y_dev, self.hidden_units, self.seed, self._call,
+                                      self.batch_size, self.likelihood_scaling, self.prior_std, x, want_grad=want_grad)
+        if x.shape[0] >= 1:
+            self._call += 1
+        return lp, grad
+
+    def log_density(self, x):
+        return self._evaluate(x, False)[0]
+
+    def log_density_and_grad(self, x):
+        return self._evaluate(x, True)
+
+    def predict(self, samples, features):
+        """Network outputs [S, M] of the weight vectors ``samples`` [S, D] on the rows ``features`` [M, F]."""
+        return hip_ops.bnn_predict(self.ctx, self.hidden_units, self.ctx.asarray(samples),
+                                   self.ctx.asarray(np.asarray(features, np.float32)))
+
+    def bayesian_inference_loss(self, samples, dataset):
+        """bnn.py:290-310: the outputs averaged over the samples, then the MSE and the RMSE of every batch of
+        ``batch_size`` rows (stored order, the last batch partial), averaged over the batches -> (loss, rmse)."""
+        features, labels = self.eval_sets[dataset]
+        out = self.predict(samples, features)
+        mean_out = (out.numpy() if hasattr(out, "numpy") else np.asarray(out)).astype(np.float64).mean(0)
+        losses = []
+        for b0 in range(0, len(labels), self.batch_size):
+            r = labels[b0:b0 + self.batch_size].astype(np.float64) - mean_out[b0:b0 + self.batch_size]
+            losses.append(np.mean(r * r))
+        losses = np.asarray(losses)
+        return float(losses.mean()), float(np.sqrt(losses).mean())
+
+    def expensive_metrics(self, model, samples) -> dict:
+        """bnn.py:417-444, keys as upstream names them (``bi_test_accuracy`` is an RMSE)."""
+        metrics = dict()
+        if "test" in self.eval_sets:
+            loss, rmse = self.bayesian_inference_loss(samples, "test")
+            metrics.update({"bi_test_loss": loss, "bi_test_accuracy": rmse})
+        if "vali" in self.eval_sets:
+            loss, rmse = self.bayesian_inference_loss(samples, "vali")
+            metrics.update({"bi_vali_loss": loss, "bi_vali_rmse": rmse})
+        return metrics
+
+
+def resolve_dataset_dir(dataset_dir=None):
+    d = dataset_dir if dataset_dir is not None else os.environ.get(DATASET_DIR_ENV)
+    if not d:
+        raise FileNotFoundError(
+            f"no dataset directory for the WINE target: set environment_config['dataset_dir'] or the {DATASET_DIR_ENV} "
+            f"environment variable to a directory holding {WINE_FILE.format('<dataset_seed % 10>')}")
+    return d
+
+
+def load_wine(dataset_seed, dataset_dir=None):
+    """The six arrays of ``wine/wine_seed_{dataset_seed % 10}.npz`` (bnn.py:395-404)."""
+    path = os.path.join(resolve_dataset_dir(dataset_dir), WINE_FILE.format(int(dataset_seed) % 10))
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} does not exist: the dataset directory (environment_config['dataset_dir'] or "
+                                f"{DATASET_DIR_ENV}) must hold {WINE_FILE.format(int(dataset_seed) % 10)}")
+    with np.load(path, allow_pickle=False) as z:
+        return {k: z[k] for k in WINE_ARRAYS}
+
+
+class BNN_WINE(BNNRegression):
+    """bnn.py:385-444: 11 -> 8 -> 8 -> 1 on the wine-quality split ``dataset_seed % 10``; ``seed`` keys the minibatch
+    stream (default: the dataset seed, which is the run seed when built by name)."""
+
+    def __init__(self, dataset_seed, likelihood_scaling, prior_std, batch_size, dataset_dir=None, seed=None):
+        data = load_wine(dataset_seed, dataset_dir)
+        self.dataset_seed = int(dataset_seed)
+        super().__init__(data["features_train"], data["labels_train"], hidden_units=(8, 8),
+                         likelihood_scaling=likelihood_scaling, prior_std=prior_std, batch_size=batch_size,
+                         seed=self.dataset_seed if seed is None else seed,
+                         eval_sets={"test": (data["features_test"], data["labels_test"]),
+                                    "vali": (data["features_vali"], data["labels_vali"])})
+
+
+def make_WINE_target(likelihood_scaling, dataset_seed, prior_std, batch_size, dataset_dir=None, seed=None):
+    return BNN_WINE(dataset_seed=dataset_seed, likelihood_scaling=likelihood_scaling, prior_std=prior_std,
+                    batch_size=batch_size, dataset_dir=dataset_dir, seed=seed)

@@ -105,6 +105,39 @@ def target_logreg(ctx, A, prior_mean, prior_std, x, want_grad=True):
     return lp, grad
 
 
+def target_bnn(ctx, X, y, hidden_units, seed, call, batch_size, likelihood_scaling, prior_std, x, want_grad=True):
+    """Bayesian-neural-network regression posterior (csrc/bnn.hip).  X: [T, F] training features, y: [T] labels,
+    hidden_units (H1, H2); the minibatch rows come from the stream of (seed, call).  -> (lp [n], grad [n, D])."""
+    t, f = X.shape
+    h1, h2 = (int(h) for h in hidden_units)
+    d = f * h1 + h1 + h1 * h2 + h2 + h2 + 1
+    n = x.shape[0]
+    _req(X, (t, f), name="X"); _req(y, (t,), name="y"); _req(x, (n, d), name="x")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_bnn(ctx.handle, f, h1, h2, t, X.ptr, y.ptr, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(call) & 0xFFFFFFFF, int(batch_size), float(likelihood_scaling),
+                                           float(prior_std), x.ptr, n, lp.ptr, None if grad is None else grad.ptr))
+    return lp, grad
+
+
+def bnn_predict(ctx, hidden_units, W, X):
+    """Network outputs of every weight vector on every row (csrc/bnn.hip), forward only.  W: [S, D], X: [M, F] -> [S, M]."""
+    m, f = X.shape
+    h1, h2 = (int(h) for h in hidden_units)
+    d = f * h1 + h1 + h1 * h2 + h2 + h2 + 1
+    s = W.shape[0]
+    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
+    out = ctx.empty((s, m))
+    if m > 0:
+        for s0 in range(0, s, 65535):                   # the kernel's grid takes at most 65535 weight vectors per launch
+            s1 = min(s, s0 + 65535)
+            ctx.check(ctx.lib.gmmvi_bnn_predict(ctx.handle, f, h1, h2, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m,
+                                                out.rows(s0, s1).ptr))
+    return out
+
+
 def sample_components(ctx, means, chols, offsets, n, seed=0, first_index=0, stream_id=0, eps=None):
     """offsets: DeviceArray int32 [K+1] prefix sums with offsets[K] == n.  -> (x [n,D], mapping [n] int32)."""
     k, d = means.shape

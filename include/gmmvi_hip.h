@@ -195,6 +195,22 @@ int gmmvi_target_planar(gmmvi_ctx* ctx, int D, const float* prior_std_dev, int G
 int gmmvi_target_logreg(gmmvi_ctx* ctx, int D, int M, const float* A_dev, float prior_mean, float prior_std,
                         const float* W_dev, int N, float* lp_out_dev, float* grad_out_dev);
 
+/* Bayesian-neural-network regression (target_distributions/bnn.py:59-311,385-448, the WINE posterior) and its analytic
+ * gradient.  Network F -> H1 -> H2 -> 1 (sigmoid, sigmoid, linear); W_dev[N,D] in the reference's layout W1 [F,H1]
+ * row-major, b1 [H1], W2 [H1,H2], b2 [H2], W3 [H2], b3, so D = F H1 + H1 + H1 H2 + H2 + H2 + 1.  X_dev[T,F], y_dev[T]:
+ * the training set.  Sample n sees the B rows pi_{seed,call,e}(p mod T), p = n B + j, e = p div T (the Feistel/Philox
+ * minibatch stream of csrc/bnn.hip, stream id 3):
+ *   lp[n]   = likelihood_scaling (-(T/B) sum_j (y - f(x; w_n))^2 - 0.5 sum_d w_nd^2 / prior_std^2)
+ *   grad[n] = d lp[n] / d w_n
+ * grad_out_dev may be NULL.  1 <= F <= 32, 1 <= H1, H2 <= 16, 1 <= B <= T; anything else: GMMVI_ERR_ARG. */
+int gmmvi_target_bnn(gmmvi_ctx* ctx, int F, int H1, int H2, int T, const float* X_dev, const float* y_dev, uint64_t seed,
+                     uint32_t call, int B, float likelihood_scaling, float prior_std, const float* W_dev, int N,
+                     float* lp_out_dev, float* grad_out_dev);
+
+/* The same network's outputs, forward only: out[s, m] = f(X[m]; W[s]).  W_dev[S,D], X_dev[M,F], S <= 65535. */
+int gmmvi_bnn_predict(gmmvi_ctx* ctx, int F, int H1, int H2, const float* W_dev, int S, const float* X_dev, int M,
+                      float* out_dev);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
