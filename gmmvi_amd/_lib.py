@@ -94,6 +94,7 @@ _PROTOS = {
     "gmmvi_mixture_eval_dual": (_i, [_p, _i, _f, _i, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p]),
     "gmmvi_target_planar": (_i, [_p, _i, _p, _i, _p, _f, _p, _i, _p, _p]),
     "gmmvi_target_logreg": (_i, [_p, _i, _i, _p, _f, _f, _p, _i, _p, _p]),
+    "gmmvi_target_logreg_mb": (_i, [_p, _i, _i, _p, _i, _i, _u64, _u32, _f, _f, _p, _i, _p, _p]),
     "gmmvi_target_bnn": (_i, [_p, _i, _i, _i, _i, _p, _p, _u64, _u32, _i, _f, _f, _p, _i, _p, _p]),
     "gmmvi_bnn_predict": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),

@@ -63,6 +63,10 @@ EXPERIMENT_DEFAULTS = {
     "planar_robot_4": _experiment("PlanarRobot4", {}, 300, [1.] + [0.2] * 9, [0.0625] + [0.0025] * 9, 10),
     "breast_cancer": _experiment("breastCancer", {}, 1, 10., 100., 50),
     "german_credit": _experiment("GermanCredit", {}, 1, 10., 100., 20),
+    "breast_cancer_mb": _experiment("breastCancer_mb", {"batch_size": 64, "size_test_set": 0,
+                                                        "use_own_batch_per_sample": True}, 1, 10., 100., 20),
+    "german_credit_mb": _experiment("GermanCredit_mb", {"batch_size": 64, "size_test_set": 0,
+                                                        "use_own_batch_per_sample": True}, 1, 10., 100., 20),
     "wine": _experiment("WINE", {"likelihood_scaling": 1., "prior_std": 1., "batch_size": 128}, 4, 1., 1., 25,
                         max_db=500000),
 }

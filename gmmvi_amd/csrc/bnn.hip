@@ -9,7 +9,8 @@
 //
 // Minibatch stream: row j of sample n's batch has stream position p = n B + j, epoch e = p div T and rank
 // r = p mod T; its data row is pi_{seed,call,e}(r), a 4-round balanced Feistel network on 2h bits (h = ceil(ceil(log2 T)
-// / 2), cycle walking) whose round function is word 0 of Philox4x32-10 (philox.h) with counter (R | i << 24, e, call, 3).
+// / 2), cycle walking) whose round function is word 0 of Philox4x32-10 (philox.h) with counter (R | i << 24, e, call, 3)
+// (feistel.h).
 // Each lane computes its own index; no sort, no device state.
 //
 // Mapping: one workgroup per sample, one batch row per lane (128 rows per chunk; B > 128 loops over chunks).  The sample's
@@ -19,7 +20,7 @@
 // owns the entries t, t + 128, ...; it sums them over the chunk's rows in row order, so the result is bitwise reproducible
 // (no atomics).  The prior term and the loss are summed over the workgroup by fixed-order DPP reductions.
 #include "common.h"
-#include "philox.h"
+#include "feistel.h"
 #include "wave_reduce.h"
 
 namespace {
@@ -48,25 +49,6 @@ __host__ __device__ inline BnnShape bnn_shape(int F, int H1, int H2) {
 __device__ __forceinline__ float bnn_sigmoid(float z) {
     const float e = expf(-fabsf(z));
     return (z >= 0.f ? 1.f : e) / (1.f + e);
-}
-
-// pi_{seed,call,e}(r): the Feistel bijection of [0, 2^(2h)) walked until it lands in [0, T)
-__device__ __forceinline__ uint32_t bnn_permute(uint32_t r, uint32_t e, uint32_t call, uint32_t T, uint32_t h, uint32_t k0,
-                                                uint32_t k1) {
-    const uint32_t mask = (1u << h) - 1u;
-    uint32_t x = r;
-    do {
-        uint32_t L = x >> h, R = x & mask;
-#pragma unroll
-        for (uint32_t i = 0; i < 4; ++i) {
-            const uint32_t f = philox4x32_10(R | (i << 24), e, call, BNN_STREAM_MINIBATCH, k0, k1).w[0] & mask;
-            const uint32_t nl = R;
-            R = L ^ f;
-            L = nl;
-        }
-        x = (L << h) | R;
-    } while (x >= T);
-    return x;
 }
 
 // forward pass of one row; EXACT: the shape is (FM, H1M, H2M) at compile time
@@ -149,7 +131,7 @@ __global__ __launch_bounds__(BNN_THREADS) void bnn_target_kernel(int F_, int H1_
         if (t < rows) {
             uint32_t r = r_base + (uint32_t)(c0 + t), e = e_base;    // r_base + j < 2T since j < B <= T
             if (r >= (uint32_t)T) { r -= (uint32_t)T; ++e; }
-            const uint32_t row = bnn_permute(r, e, call, (uint32_t)T, h, k0, k1);
+            const uint32_t row = gmmvi_feistel_permute(r, e, call, BNN_STREAM_MINIBATCH, (uint32_t)T, h, k0, k1);
             float x[FM], h1[H1M], h2[H2M];
 #pragma unroll
             for (int i = 0; i < FM; ++i) x[i] = i < F ? X[(size_t)row * F + i] : 0.f;
@@ -248,9 +230,7 @@ extern "C" int gmmvi_target_bnn(gmmvi_ctx* ctx, int F, int H1, int H2, int T, co
     if (N == 0) return GMMVI_OK;
     GMMVI_ARG_CHECK(ctx, X_dev && y_dev && W_dev && lp_out_dev);
     GMMVI_PROF(ctx, "target_bnn");
-    uint32_t bits = 0;
-    while ((1ull << bits) < (uint64_t)T) ++bits;                       // ceil(log2 T)
-    const uint32_t h = (bits + 1) / 2;
+    const uint32_t h = gmmvi_feistel_half_bits((uint32_t)T);
     const BnnShape sh = bnn_shape(F, H1, H2);
     const size_t shmem = ((size_t)((sh.D + 3) & ~3) + (size_t)BNN_THREADS * sh.RS) * sizeof(float);   // <= 54 KB
     const float inv_var = 1.f / (prior_std * prior_std);

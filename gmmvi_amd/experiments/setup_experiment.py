@@ -18,9 +18,11 @@ _MAX_REWARD_HISTORY = 10000        # setup_experiment.py:40-41
 
 # the factory takes the environment config and the run seed as ``dataset_seed`` (setup_experiment.py:77-79 upstream)
 CONFIG_AND_SEED = "config+seed"
+# the factory takes the environment config and the run seed as ``seed`` (the key of its minibatch stream)
+CONFIG_AND_RUN_SEED = "config+run_seed"
 
 # experiment name (exact, or prefix when the key ends with "*") -> (module below target_distributions, factory, takes the
-# config: True, False or CONFIG_AND_SEED)
+# config: True, False, CONFIG_AND_SEED or CONFIG_AND_RUN_SEED)
 _TARGETS = {
     "PlanarRobot4": ("planar_robot", "make_four_goal", False),
     "PlanarRobot1": ("planar_robot", "make_single_goal", False),
@@ -29,11 +31,14 @@ _TARGETS = {
     "DIAGGMM*": ("diag_gmm", "make_target", True),
     "breastCancer": ("logistic_regression", "make_breast_cancer", True),
     "GermanCredit": ("logistic_regression", "make_german_credit", True),
+    "breastCancer_mb": ("logistic_regression", "make_breast_cancer_mb", CONFIG_AND_RUN_SEED),
+    "GermanCredit_mb": ("logistic_regression", "make_german_credit_mb", CONFIG_AND_RUN_SEED),
     "WINE*": ("bnn", "make_WINE_target", CONFIG_AND_SEED),
 }
 
-# the reference's minibatch logistic-regression variants (logistic_regression.py:70-142): out of scope
-_UNSUPPORTED = ("breastCancer_mb", "GermanCredit_mb")
+# environment_config keys without which a target cannot be built (upstream's factories take them without defaults)
+_MINIBATCH_KEYS = ("batch_size", "size_test_set", "use_own_batch_per_sample")
+_REQUIRED_CONFIG = {"breastCancer_mb": _MINIBATCH_KEYS, "GermanCredit_mb": _MINIBATCH_KEYS}
 
 
 def _lookup_target(experiment):
@@ -48,23 +53,26 @@ def _lookup_target(experiment):
 
 
 def get_target_lnpdf(experiment, environment_config, seed):
-    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit, WINE* (``environment_config``
-    may name the ``dataset_dir``; WINE takes ``seed`` as its dataset seed and as the seed of its minibatch stream); the
-    reference's other benchmark posteriors (the minibatch logistic regressions, MNIST, Talos) plug in as
-    ``config['target_fn']`` through the LNPDF interface."""
-    if experiment in _UNSUPPORTED:
-        raise ValueError(f"get_target_lnpdf(): the minibatch variant {experiment} is not supported by this build (the full-data "
-                         f"posterior {experiment[:-3]} is); pass such a target as config['target_fn']")
+    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*
+    (``environment_config`` may name the ``dataset_dir``; WINE takes ``seed`` as its dataset seed and as the seed of its
+    minibatch stream, the _mb variants as the seed of theirs); the reference's other benchmark posteriors (MNIST, Talos)
+    plug in as ``config['target_fn']`` through the LNPDF interface."""
+    missing = [k for k in _REQUIRED_CONFIG.get(experiment, ()) if k not in environment_config]
+    if missing:
+        raise ValueError(f"get_target_lnpdf(): the minibatch variant {experiment} needs {', '.join(missing)} in "
+                         f"environment_config; calling it without them is not supported")
     entry = _lookup_target(experiment)
     if entry is None:
         raise ValueError(f"get_target_lnpdf() was called with unknown experiment name: {experiment} "
-                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer, GermanCredit, WINE*; pass other "
-                         f"targets as config['target_fn'])")
+                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*; "
+                         f"pass other targets as config['target_fn'])")
     module_name, factory_name, takes_config = entry
     module = importlib.import_module(f"{__package__}.target_distributions.{module_name}")
     factory = getattr(module, factory_name)
     if takes_config == CONFIG_AND_SEED:
         return factory(dataset_seed=seed, **environment_config)
+    if takes_config == CONFIG_AND_RUN_SEED:
+        return factory(seed=seed, **environment_config)
     return factory(**environment_config) if takes_config else factory()
 
 

@@ -57,8 +57,9 @@ def feistel_half_bits(num_data):
     return (bits + 1) // 2
 
 
-def permute_rows(seed, call, epoch, rank, num_data):
-    """pi_{seed,call,epoch}(rank) for int arrays epoch, rank (rank < num_data) -> int64 rows."""
+def permute_rows(seed, call, epoch, rank, num_data, stream=STREAM_MINIBATCH):
+    """pi_{seed,call,epoch}(rank) for int arrays epoch, rank (rank < num_data) -> int64 rows.  ``stream`` is the counter's
+    last word: 3 (the default) for these minibatches, 4 for the minibatch logistic regressions."""
     h = feistel_half_bits(num_data)
     mask = np.uint64((1 << h) - 1)
     x = np.asarray(rank, np.uint64).copy()
@@ -70,7 +71,7 @@ def permute_rows(seed, call, epoch, rank, num_data):
     while todo.size:
         L, R = xt >> np.uint64(h), xt & mask
         for i in range(4):
-            f = _philox_word0(R | np.uint64(i << 24), et, np.full_like(R, c), np.full_like(R, STREAM_MINIBATCH), seed)
+            f = _philox_word0(R | np.uint64(i << 24), et, np.full_like(R, c), np.full_like(R, int(stream)), seed)
             L, R = R, L ^ (f & mask)
         xt = (L << np.uint64(h)) | R
         x[todo] = xt

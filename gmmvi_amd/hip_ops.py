@@ -105,6 +105,21 @@ def target_logreg(ctx, A, prior_mean, prior_std, x, want_grad=True):
     return lp, grad
 
 
+def target_logreg_mb(ctx, A, batch_size, num_batches, seed, call, prior_mean, prior_std, x, want_grad=True):
+    """Minibatch logistic-regression posterior (csrc/logreg_mb.hip).  A: [T, D] signed training rows; sample n takes batch
+    n mod num_batches of the permutation of (seed, call).  -> (lp [n], grad [n, D])."""
+    t, d = A.shape
+    n = x.shape[0]
+    _req(A, (t, d), name="A"); _req(x, (n, d), name="x")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_logreg_mb(ctx.handle, d, t, A.ptr, int(batch_size), int(num_batches),
+                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, float(prior_mean),
+                                                 float(prior_std), x.ptr, n, lp.ptr, None if grad is None else grad.ptr))
+    return lp, grad
+
+
 def target_bnn(ctx, X, y, hidden_units, seed, call, batch_size, likelihood_scaling, prior_std, x, want_grad=True):
     """Bayesian-neural-network regression posterior (csrc/bnn.hip).  X: [T, F] training features, y: [T] labels,
     hidden_units (H1, H2); the minibatch rows come from the stream of (seed, call).  -> (lp [n], grad [n, D])."""

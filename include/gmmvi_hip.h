@@ -195,6 +195,18 @@ int gmmvi_target_planar(gmmvi_ctx* ctx, int D, const float* prior_std_dev, int G
 int gmmvi_target_logreg(gmmvi_ctx* ctx, int D, int M, const float* A_dev, float prior_mean, float prior_std,
                         const float* W_dev, int N, float* lp_out_dev, float* grad_out_dev);
 
+/* The minibatch variant (target_distributions/logistic_regression.py:70-142, LogisticRegression_minibatch) on the T
+ * training rows A_dev[T,D] (signed, as above).  Within call `call` the rows are permuted by rho (the Feistel/Philox
+ * permutation of DESIGN.md 6 keyed by seed, counter (R | i << 24, 0, call, 4): stream id 4) and sample n takes the batch
+ * b = n mod nb of B rows, row(n, j) = rho(b B + j):
+ *   lp[n]   = (T/B) sum_j log sigmoid(a_row(n,j) . w_n) + sum_d log N(w_nd; prior_mean, prior_std^2)
+ *   grad[n] = (T/B) sum_j sigmoid(-a_row(n,j) . w_n) a_row(n,j) - (w_n - prior_mean) / prior_std^2
+ * W_dev[N,D]; grad_out_dev may be NULL; N == 0 launches nothing.  1 <= D <= 128, 1 <= B <= T, nb >= 1, nb B <= T,
+ * prior_std > 0; anything else: GMMVI_ERR_ARG.  Bitwise reproducible for a given (seed, call). */
+int gmmvi_target_logreg_mb(gmmvi_ctx* ctx, int D, int T, const float* A_dev, int B, int nb, uint64_t seed, uint32_t call,
+                           float prior_mean, float prior_std, const float* W_dev, int N, float* lp_out_dev,
+                           float* grad_out_dev);
+
 /* Bayesian-neural-network regression (target_distributions/bnn.py:59-311,385-448, the WINE posterior) and its analytic
  * gradient.  Network F -> H1 -> H2 -> 1 (sigmoid, sigmoid, linear); W_dev[N,D] in the reference's layout W1 [F,H1]
  * row-major, b1 [H1], W2 [H1,H2], b2 [H2], W3 [H2], b3, so D = F H1 + H1 + H1 H2 + H2 + H2 + 1.  X_dev[T,F], y_dev[T]:
