@@ -69,4 +69,5 @@ EXPERIMENT_DEFAULTS = {
                                                         "use_own_batch_per_sample": True}, 1, 10., 100., 20),
     "wine": _experiment("WINE", {"likelihood_scaling": 1., "prior_std": 1., "batch_size": 128}, 4, 1., 1., 25,
                         max_db=500000),
+    "talos": _experiment("Talos", {"context": [0.1, 0.5, 1.]}, 1, 1., 1., 500, max_db=500000),
 }

@@ -55,8 +55,9 @@ extern "C" int gmmvi_train_iter_samtron(gmmvi_ctx* ctx, const gmmvi_samtron_plan
 
 static int train_iter_samtron_body(gmmvi_ctx* ctx, const gmmvi_samtron_plan* p) {
     GMMVI_ARG_CHECK(ctx, p != nullptr);
-    GMMVI_ARG_CHECK(ctx, p->target_kind >= 0 && p->target_kind <= 2);        // 0 mixture, 1 planar robot, 2 logistic regression
+    GMMVI_ARG_CHECK(ctx, (p->target_kind >= 0 && p->target_kind <= 2) || p->target_kind == 4);  // 0 mixture, 1 planar robot, 2 logistic regression, 4 Talos
     GMMVI_ARG_CHECK(ctx, p->target_kind != 2 || (p->logreg_A && p->logreg_M >= 1 && p->logreg_prior_std > 0.f));
+    GMMVI_ARG_CHECK(ctx, p->target_kind != 4 || (p->talos_model && p->talos_context && p->D == 34));
     const int K = p->K, D = p->D, N = p->N;
     GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D < GMMVI_MAX_DIM && N >= 1);
     GMMVI_ARG_CHECK(ctx, p->means && p->chols && p->logw && p->packed && p->packed_new && p->stepsizes && p->last_eta &&
@@ -163,6 +164,8 @@ static int train_iter_samtron_body(gmmvi_ctx* ctx, const gmmvi_samtron_plan* p) 
     } else if (p->target_kind == 2) {
         GMMVI_TRY(gmmvi_target_logreg(ctx, D, p->logreg_M, p->logreg_A, p->logreg_prior_mean, p->logreg_prior_std, x, N,
                                       p->db_tlp, p->db_tgrad));
+    } else if (p->target_kind == 4) {
+        GMMVI_TRY(gmmvi_target_talos(ctx, p->talos_model, p->talos_context, x, N, p->db_tlp, p->db_tgrad));
     } else {
         ctx->prof_tag = "sweep_target";
         int rc_t = gmmvi_mixture_eval(ctx, p->target_family, p->target_nu, p->target_K, D, p->target_packed,
@@ -259,6 +262,8 @@ static int sharded_phase_body(gmmvi_ctx* ctx, const gmmvi_sharded_plan* p, int p
         } else if (p->target_kind == 2) {
             GMMVI_TRY(gmmvi_target_logreg(ctx, D, p->logreg_M, p->logreg_A, p->logreg_prior_mean, p->logreg_prior_std, x_loc, Nl,
                                           tlp_loc, tgrad_loc));
+        } else if (p->target_kind == 4) {
+            GMMVI_TRY(gmmvi_target_talos(ctx, p->talos_model, p->talos_context, x_loc, Nl, tlp_loc, tgrad_loc));
         } else {
             ctx->prof_tag = "sweep_target";
             int rc_t = gmmvi_mixture_eval(ctx, p->target_family, p->target_nu, p->target_K, D, p->target_packed, p->target_logw,
@@ -356,8 +361,9 @@ static int sharded_phase_body(gmmvi_ctx* ctx, const gmmvi_sharded_plan* p, int p
 
 extern "C" int gmmvi_train_iter_sharded_phase(gmmvi_ctx* ctx, const gmmvi_sharded_plan* p, int phase) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr && p != nullptr && phase >= 1 && phase <= 4);
-    GMMVI_ARG_CHECK(ctx, p->target_kind >= 0 && p->target_kind <= 2);        // 0 mixture, 1 planar robot, 2 logistic regression
+    GMMVI_ARG_CHECK(ctx, (p->target_kind >= 0 && p->target_kind <= 2) || p->target_kind == 4);  // 0 mixture, 1 planar robot, 2 logistic regression, 4 Talos
     GMMVI_ARG_CHECK(ctx, p->target_kind != 2 || (p->logreg_A && p->logreg_M >= 1 && p->logreg_prior_std > 0.f));
+    GMMVI_ARG_CHECK(ctx, p->target_kind != 4 || (p->talos_model && p->talos_context && p->D == 34));
     GMMVI_ARG_CHECK(ctx, p->n_ranks >= 1 && p->rank >= 0 && p->rank < p->n_ranks && p->K >= 1 && p->D >= 1 && p->D < GMMVI_MAX_DIM &&
                              p->N >= p->n_ranks && p->N % p->n_ranks == 0);
     GMMVI_ARG_CHECK(ctx, p->means && p->chols && p->packed && p->packed_new && p->stepsizes && p->last_eta && p->l2 && p->num_updates &&

@@ -34,6 +34,7 @@ _TARGETS = {
     "breastCancer_mb": ("logistic_regression", "make_breast_cancer_mb", CONFIG_AND_RUN_SEED),
     "GermanCredit_mb": ("logistic_regression", "make_german_credit_mb", CONFIG_AND_RUN_SEED),
     "WINE*": ("bnn", "make_WINE_target", CONFIG_AND_SEED),
+    "Talos*": ("talos_ik", "make_talos_target", True),
 }
 
 # environment_config keys without which a target cannot be built (upstream's factories take them without defaults)
@@ -53,10 +54,10 @@ def _lookup_target(experiment):
 
 
 def get_target_lnpdf(experiment, environment_config, seed):
-    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*
+    """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*, Talos*
     (``environment_config`` may name the ``dataset_dir``; WINE takes ``seed`` as its dataset seed and as the seed of its
-    minibatch stream, the _mb variants as the seed of theirs); the reference's other benchmark posteriors (MNIST, Talos)
-    plug in as ``config['target_fn']`` through the LNPDF interface."""
+    minibatch stream, the _mb variants as the seed of theirs; Talos takes the left gripper's goal as ``context``); the
+    reference's other benchmark posterior (MNIST) plugs in as ``config['target_fn']`` through the LNPDF interface."""
     missing = [k for k in _REQUIRED_CONFIG.get(experiment, ()) if k not in environment_config]
     if missing:
         raise ValueError(f"get_target_lnpdf(): the minibatch variant {experiment} needs {', '.join(missing)} in "
@@ -64,7 +65,7 @@ def get_target_lnpdf(experiment, environment_config, seed):
     entry = _lookup_target(experiment)
     if entry is None:
         raise ValueError(f"get_target_lnpdf() was called with unknown experiment name: {experiment} "
-                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*; "
+                         f"(in scope: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*, Talos*; "
                          f"pass other targets as config['target_fn'])")
     module_name, factory_name, takes_config = entry
     module = importlib.import_module(f"{__package__}.target_distributions.{module_name}")

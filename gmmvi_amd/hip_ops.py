@@ -153,6 +153,35 @@ def bnn_predict(ctx, hidden_units, W, X):
     return out
 
 
+TALOS_DIM = 34                                          # csrc/talos.hip: 28 joints, base position, roll / pitch / yaw
+TALOS_TABLE_SIZE = 8 + 28 * 28 + 4 * 16                 # header, joint records, tip records (talos_ik.py)
+
+
+def target_talos(ctx, model, context, x, want_grad=True):
+    """Talos inverse-kinematics target (csrc/talos.hip).  model: the packed table of talos_ik.TalosModel, context: [3] the
+    left gripper's goal, x: [n, 34].  -> (lp [n], grad [n, 34])."""
+    n = x.shape[0]
+    _req(model, (TALOS_TABLE_SIZE,), name="model"); _req(context, (3,), name="context"); _req(x, (n, TALOS_DIM), name="x")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, TALOS_DIM)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_talos(ctx.handle, model.ptr, context.ptr, x.ptr, n, lp.ptr,
+                                             None if grad is None else grad.ptr))
+    return lp, grad
+
+
+def talos_fk(ctx, model, x):
+    """Forward kinematics of the Talos model (csrc/talos.hip).  -> (poses [n, 4, 12]: per tip world position and row-major
+    rotation, com [n, 3]: world centre of mass)."""
+    n = x.shape[0]
+    _req(model, (TALOS_TABLE_SIZE,), name="model"); _req(x, (n, TALOS_DIM), name="x")
+    poses = ctx.empty((n, 4, 12))
+    com = ctx.empty((n, 3))
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_talos_fk(ctx.handle, model.ptr, x.ptr, n, poses.ptr, com.ptr))
+    return poses, com
+
+
 def sample_components(ctx, means, chols, offsets, n, seed=0, first_index=0, stream_id=0, eps=None):
     """offsets: DeviceArray int32 [K+1] prefix sums with offsets[K] == n.  -> (x [n,D], mapping [n] int32)."""
     k, d = means.shape

@@ -50,6 +50,7 @@ class SamtronPlan(C.Structure):
         ("weight_stepsize_mode", _i), ("ws_min", _f), ("ws_max", _f), ("ws_inc", _f), ("ws_dec", _f),
         ("weight_update_mode", _i), ("stein_flags", _i), ("presample_next", _i), ("presampled", _i), ("phase", _i),
         ("logreg_A", _p), ("logreg_M", _i), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
+        ("talos_model", _p), ("talos_context", _p),
     ]
 
 
@@ -211,6 +212,7 @@ class SamtronFastPath:
         p.planar_goals_count, p.planar_likelihood_std = tgt.get("G", 0), tgt.get("lik_std", 0.0)
         p.logreg_A, p.logreg_M = tgt.get("A"), tgt.get("M", 0)
         p.logreg_prior_mean, p.logreg_prior_std = tgt.get("lr_prior_mean", 0.0), tgt.get("lr_prior_std", 0.0)
+        p.talos_model, p.talos_context = tgt.get("talos_model"), tgt.get("talos_context")
         p.means, p.chols, p.logw = model.means.ptr, model.chol_cov.ptr, model.log_weights.ptr
         p.packed, p.packed_new = packed_cur.ptr, packed_new.ptr
         p.stepsizes, p.last_eta, p.l2 = m.stepsizes.ptr, m.last_log_etas.ptr, m.l2_regularizers.ptr

@@ -56,6 +56,7 @@ class ShardedPlan(_C.Structure):
         ("weight_stepsize_mode", _i), ("ws_min", _f), ("ws_max", _f), ("ws_inc", _f), ("ws_dec", _f),
         ("stein_flags", _i), ("presample_next", _i), ("presampled", _i), ("scratch", _p),
         ("logreg_A", _p), ("logreg_M", _i), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
+        ("talos_model", _p), ("talos_context", _p),
     ]
 
 
@@ -366,6 +367,7 @@ class ShardedGMMVI:
         p.planar_goals_count, p.planar_likelihood_std = t.get("G", 0), t.get("lik_std", 0.0)
         p.logreg_A, p.logreg_M = t.get("A"), t.get("M", 0)
         p.logreg_prior_mean, p.logreg_prior_std = t.get("lr_prior_mean", 0.0), t.get("lr_prior_std", 0.0)
+        p.talos_model, p.talos_context = t.get("talos_model"), t.get("talos_context")
         p.e1, p.e2, p.e3 = f.e1.ptr, f.e2.ptr, f.e3.ptr
         p.x_all, p.tlp_all, p.tgrad_all = f.x_all.ptr, f.tlp_all.ptr, f.tgrad_all.ptr
         p.E_all, p.reward_all = f.E_all.ptr, f.reward_all.ptr

@@ -223,6 +223,19 @@ int gmmvi_target_bnn(gmmvi_ctx* ctx, int F, int H1, int H2, int T, const float* 
 int gmmvi_bnn_predict(gmmvi_ctx* ctx, int F, int H1, int H2, const float* W_dev, int S, const float* X_dev, int M,
                       float* out_dev);
 
+/* Talos humanoid inverse kinematics (target_distributions/talos_ik.py; DESIGN.md 6, "Talos (defined, not reproduced)") and
+ * its analytic gradient.  model_dev: the packed f32 table of talos_ik.TalosModel (28 revolute joints, 4 tips, lumped
+ * masses); context_dev[3]: the left gripper's goal.  X_dev[N,34] = [q (28), p_b (3), roll, pitch, yaw]:
+ *   lp[n]   = joint limits + centre of mass over the left foot + right foot + left foot + left gripper (the five terms)
+ *   grad[n] = d lp[n] / d x_n (geometric Jacobian)
+ * grad_out_dev may be NULL; N == 0 launches nothing.  One lane per sample, no atomics: bitwise reproducible. */
+int gmmvi_target_talos(gmmvi_ctx* ctx, const float* model_dev, const float* context_dev, const float* X_dev, int N,
+                       float* lp_out_dev, float* grad_out_dev);
+
+/* The forward kinematics of the same model: poses_out_dev[N,4,12] = per tip (r_gripper, l_gripper, r_foot, l_foot) the
+ * world position (3) and rotation (9, row-major); com_out_dev[N,3] the world centre of mass of the 37 path links. */
+int gmmvi_talos_fk(gmmvi_ctx* ctx, const float* model_dev, const float* X_dev, int N, float* poses_out_dev, float* com_out_dev);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
@@ -329,8 +342,9 @@ int gmmvi_weight_stepsize_improvement(gmmvi_ctx* ctx, int K, const float* logw_d
  * n_old == 0 and bg_packed == NULL the background components are the model's own (one sweep for both). */
 typedef struct gmmvi_samtron_plan {
     int32_t K, D, N;                      /* components, dimension, samples of this iteration (sum of the counts) */
-    int32_t target_kind;                  /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot, 2: logistic regression;
-                                           * any other value: GMMVI_ERR_ARG */
+    int32_t target_kind;                  /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot, 2: logistic regression,
+                                           * 4: Talos (gmmvi_target_talos); any other value, 3 included (no target has it):
+                                           * GMMVI_ERR_ARG */
     int32_t target_family, target_K;      /* enum gmmvi_family, number of target components */
     float target_nu;
     const float* target_packed;           /* [target_K, stride] */
@@ -391,6 +405,9 @@ typedef struct gmmvi_samtron_plan {
     const float* logreg_A;
     int32_t logreg_M;
     float logreg_prior_mean, logreg_prior_std;
+    /* target_kind 4 (gmmvi_target_talos): the packed model table, the left gripper's goal [3] */
+    const float* talos_model;
+    const float* talos_context;
 } gmmvi_samtron_plan;
 int gmmvi_train_iter_samtron(gmmvi_ctx* ctx, const gmmvi_samtron_plan* plan);
 
@@ -453,6 +470,9 @@ typedef struct gmmvi_sharded_plan {
     const float* logreg_A;
     int32_t logreg_M;
     float logreg_prior_mean, logreg_prior_std;
+    /* target_kind 4: as in gmmvi_samtron_plan */
+    const float* talos_model;
+    const float* talos_context;
 } gmmvi_sharded_plan;
 size_t gmmvi_sharded_scratch_floats(int K, int D, int N);
 int gmmvi_train_iter_sharded_phase(gmmvi_ctx* ctx, const gmmvi_sharded_plan* plan, int phase /* 1..4 */);
