@@ -460,7 +460,7 @@ __global__ void logaddexp_f32_kernel(float* __restrict__ dst, const float* __res
     for (; i < n; i += stride) {
         const float x = a[i] + ca, y = b[i] + cb;
         const float m = fmaxf(x, y);
-        dst[i] = m + logf(expf(x - m) + expf(y - m));
+        dst[i] = m == -INFINITY ? m : m + logf(expf(x - m) + expf(y - m));    // (both -inf: not (-inf) - (-inf) = NaN)
     }
 }
 
@@ -487,7 +487,9 @@ __global__ void segment_lse_kernel(const int32_t* __restrict__ off, const float*
     for (int j = off[g]; j < j1; j += 8) {
         float v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = j + u < j1 ? logw[j + u] + ld[(size_t)(j + u) * N + n] : -3.0e38f;
+        // (the slots past the segment's end hold -inf, not a finite stand-in: that one would count as a term exp(0) = 1 in
+        // a round whose log weights are all -inf)
+        for (int u = 0; u < 8; ++u) v[u] = j + u < j1 ? logw[j + u] + ld[(size_t)(j + u) * N + n] : -INFINITY;
         float mr = v[0];
 #pragma unroll
         for (int u = 1; u < 8; ++u) mr = fmaxf(mr, v[u]);

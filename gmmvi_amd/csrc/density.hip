@@ -383,9 +383,10 @@ __global__ __launch_bounds__(DP >= GMMVI_ME_WIDE_DP ? 512 : GMMVI_ME_THREADS, GM
 //  * x does not live in registers: the tile sits in LDS in pair order ([dimension pair][lane] -> x_A[2i], x_B[2i], x_A[2i+1],
 //    x_B[2i+1]: one conflict-free ds_read_b128 per dimension pair and pass), which keeps the gradient instance under 128
 //    registers = four waves per SIMD.
-//  * log-sum-exp against the running maximum of the component log densities alone (the weights enter as factors exp(log w),
-//    >= 1e-30 by the floor of the weight update): ONE exp per sample and pass serves the model mixture, the second mixture of
-//    the dual sweep and the rescaling of the gradient sums (the one-sample kernel pays four).
+//  * log-sum-exp against the running maximum of ld + log w: ONE exp per sample and pass serves the mixture and the rescaling
+//    of the gradient sums; the second mixture of the dual sweep keeps its own maximum and pays one more (the one-sample
+//    kernel pays four).  (Weights as factors exp(log w) against a maximum of ld alone would save that exp, but any log
+//    weight below -87 -- the C ABI, target mixtures and the dual sweep's second weights accept them -- would vanish.)
 //  * the waves of a workgroup are merged by a tree through four LDS slots (eight for more than 8 waves; a wave writes the
 //    slot it has just read: no barrier between a stage's reads and the next stage's writes), 47 KB instead of the 94 KB a
 //    flat merge of 128 samples would take, so that two 8-wave workgroups share a CU.
@@ -447,7 +448,7 @@ __global__ __launch_bounds__(DP > 24 ? 512 : 1024) void mixture_eval_pk_kernel(f
     ME_LDS_BARRIER();
     PK_STAMP();                                        // 1: x tile staged
 
-    pk_f32x2 mld = pk_splat(-3.0e38f), s = pk_splat(0.f), s2 = pk_splat(0.f);
+    pk_f32x2 mld = pk_splat(-3.0e38f), s = pk_splat(0.f), mld2 = pk_splat(-3.0e38f), s2 = pk_splat(0.f);
     const bool dual = logw2 != nullptr;
     pk_f32x2 acc[GRAD ? DP : 1];
     if (GRAD) {
@@ -462,8 +463,8 @@ __global__ __launch_bounds__(DP > 24 ? 512 : 1024) void mixture_eval_pk_kernel(f
 
     for (int k = k_lo + wslot; k < K; k += nwaves) {
         const sp_block_ptr blk = sp_block(packed + (size_t)k * PK::STRIDE);
-        const float w = __expf(((sp_const_f32)(uintptr_t)logw)[k]);
-        const float w2 = dual ? __expf(((sp_const_f32)(uintptr_t)logw2)[k]) : 0.f;
+        const float lw = ((sp_const_f32)(uintptr_t)logw)[k];
+        const float lw2 = dual ? ((sp_const_f32)(uintptr_t)logw2)[k] : 0.f;
         pk_f32x2 z[DP], q;
         float cst;
         float pc[2][32];
@@ -485,18 +486,25 @@ __global__ __launch_bounds__(DP > 24 ? 512 : 1024) void mixture_eval_pk_kernel(f
             ld = pk_f32x2{cst - 0.5f * nud * log1pf(q.x / nu), cst - 0.5f * nud * log1pf(q.y / nu)};
             coef = pk_f32x2{-nud / (nu + q.x), -nud / (nu + q.y)};
         }
-        // running maximum of the log densities; exactly one of (rescale factor, new term) is exp(-|d|), the other is 1
-        const pk_f32x2 d = ld - mld;
+        // running maximum of ld + log w; exactly one of (rescale factor, new term) is exp(-|d|), the other is 1
+        const pk_f32x2 a = ld + pk_splat(lw);
+        const pk_f32x2 d = a - mld;
         const float tA = __expf(-fabsf(d.x)), tB = __expf(-fabsf(d.y));
         const pk_f32x2 sc = pk_f32x2{d.x > 0.f ? tA : 1.f, d.y > 0.f ? tB : 1.f};
         const pk_f32x2 e = pk_f32x2{d.x > 0.f ? 1.f : tA, d.y > 0.f ? 1.f : tB};
-        mld = pk_f32x2{fmaxf(mld.x, ld.x), fmaxf(mld.y, ld.y)};
-        const pk_f32x2 we = e * pk_splat(w);
-        s = pk_fma(s, sc, we);
-        if (dual) s2 = pk_fma(s2, sc, e * pk_splat(w2));
+        mld = pk_f32x2{fmaxf(mld.x, a.x), fmaxf(mld.y, a.y)};
+        s = pk_fma(s, sc, e);
+        if (dual) {                                    // the second mixture keeps its own maximum: two more exps per pass
+            const pk_f32x2 a2 = ld + pk_splat(lw2);
+            const pk_f32x2 d2 = a2 - mld2;
+            const float uA = __expf(-fabsf(d2.x)), uB = __expf(-fabsf(d2.y));
+            s2 = pk_fma(s2, pk_f32x2{d2.x > 0.f ? uA : 1.f, d2.y > 0.f ? uB : 1.f},
+                        pk_f32x2{d2.x > 0.f ? 1.f : uA, d2.y > 0.f ? 1.f : uB});
+            mld2 = pk_f32x2{fmaxf(mld2.x, a2.x), fmaxf(mld2.y, a2.y)};
+        }
         if constexpr (GRAD) {
             PkPass<DP>::backward(blkb, z, pc);
-            const pk_f32x2 ec = we * coef;
+            const pk_f32x2 ec = e * coef;
 #pragma unroll
             for (int i = 0; i < DP; ++i) acc[i] = pk_fma(acc[i], sc, ec * z[i]);
             pk_pin<DP>(acc);
@@ -515,21 +523,28 @@ __global__ __launch_bounds__(DP > 24 ? 512 : 1024) void mixture_eval_pk_kernel(f
 
     // ---- merge of the waves: common maximum, then a tree of sums through four slots ---------------------------------------
     constexpr int NV = (GRAD ? DP : 0) + 2;            // register pairs a wave hands over: s, s2, gradient sums
-    pk_f32x2* sm_max = reinterpret_cast<pk_f32x2*>(sm_merge);            // [nwaves][64]
-    pk_f32x2* slots = sm_max + nwaves * 64;                              // [4 or 8][NV][64]
+    pk_f32x2* sm_max = reinterpret_cast<pk_f32x2*>(sm_merge);            // [nwaves][64], the dual sweep's maxima behind
+    pk_f32x2* slots = sm_max + (dual ? 2 : 1) * nwaves * 64;             // [4 or 8][NV][64]
     const int half0 = nwaves > 8 ? 8 : 4;                                // the first stage of the tree
     sm_max[wave * 64 + lane] = mld;
+    if (dual) sm_max[(nwaves + wave) * 64 + lane] = mld2;
     ME_LDS_BARRIER();
     PK_STAMP();                                        // 9: maxima exchanged (includes the wait for the slowest wave)
-    pk_f32x2 M = mld;
+    pk_f32x2 M = mld, M2 = mld2;
     for (int wv = 0; wv < nwaves; ++wv) {
         const pk_f32x2 o = sm_max[wv * 64 + lane];
         M = pk_f32x2{fmaxf(M.x, o.x), fmaxf(M.y, o.y)};
     }
+    if (dual) {
+        for (int wv = 0; wv < nwaves; ++wv) {
+            const pk_f32x2 o = sm_max[(nwaves + wv) * 64 + lane];
+            M2 = pk_f32x2{fmaxf(M2.x, o.x), fmaxf(M2.y, o.y)};
+        }
+        s2 = s2 * pk_f32x2{__expf(mld2.x - M2.x), __expf(mld2.y - M2.y)};
+    }
     {
         const pk_f32x2 f = pk_f32x2{__expf(mld.x - M.x), __expf(mld.y - M.y)};
         s = s * f;
-        s2 = s2 * f;
         if (GRAD) {
 #pragma unroll
             for (int i = 0; i < DP; ++i) acc[i] = acc[i] * f;
@@ -571,8 +586,8 @@ __global__ __launch_bounds__(DP > 24 ? 512 : 1024) void mixture_eval_pk_kernel(f
         if (validB) lp_out[nB] = M.y + __logf(s.y);
     }
     if (dual && lp2_out != nullptr) {
-        if (validA) lp2_out[nA] = M.x + __logf(s2.x);
-        if (validB) lp2_out[nB] = M.y + __logf(s2.y);
+        if (validA) lp2_out[nA] = M2.x + __logf(s2.x);
+        if (validB) lp2_out[nB] = M2.y + __logf(s2.y);
     }
     if (GRAD && grad_out != nullptr) {
         const pk_f32x2 inv = pk_f32x2{1.f / s.x, 1.f / s.y};
@@ -1384,11 +1399,12 @@ static int launch_mixture_eval_pk(gmmvi_ctx* ctx, int family, float nu, int K, i
     static const int env_nw = getenv("GMMVI_ME_PK_NW") ? atoi(getenv("GMMVI_ME_PK_NW")) : 0;
     const int tiles = (N + 127) / 128;
     // Geometry: all workgroups resident at once (one round), and four waves per SIMD on the loaded CUs -- either ONE 16-wave
-    // workgroup per CU or TWO 8-wave workgroups (the 16-wave form takes 108 KB of LDS at D = 20).  Measured inside the iteration
-    // (profiles/r04_notes.md): north-star shape (79 tiles, K = 100) dual sweep 23.3 us at 3 chunks x 16 waves, 24.7 at 6 x 8,
-    // 28.0 at 3 x 8 (two waves per SIMD do not cover the first-touch latency of blocks the previous launch wrote on other
-    // XCDs); fewer chunks also mean fewer partials to merge.  With 157 tiles (D = 10, K = 200, N = 20 000) a 16-wave
-    // workgroup per tile fills 61 % of the CUs and two per tile need two rounds: 3 chunks x 8 waves then (27.5 against 36.4 us).
+    // workgroup per CU or TWO 8-wave workgroups (the 16-wave form takes 108 KB of LDS at D = 20, 117 KB in the dual sweep).
+    // Measured inside the iteration (profiles/r04_notes.md): north-star shape (79 tiles, K = 100) dual sweep 23.3 us at
+    // 3 chunks x 16 waves, 24.7 at 6 x 8, 28.0 at 3 x 8 (two waves per SIMD do not cover the first-touch latency of blocks
+    // the previous launch wrote on other XCDs); fewer chunks also mean fewer partials to merge.  With 157 tiles (D = 10,
+    // K = 200, N = 20 000) a 16-wave workgroup per tile fills 61 % of the CUs and two per tile need two rounds: 3 chunks x
+    // 8 waves then (27.5 against 36.4 us).
     const long cus = ctx->num_cus;
     auto chunks_for = [&](long slots) {
         long c = slots / tiles;
@@ -1416,7 +1432,8 @@ static int launch_mixture_eval_pk(gmmvi_ctx* ctx, int family, float nu, int K, i
     if (nw > kchunk) nw = kchunk;
     if (nw > 16) nw = 16;
     const int nv = (want_grad ? DP : 0) + 2;
-    size_t shmem = (size_t)(DP / 2) * 64 * 16 + (size_t)nw * 64 * 8 + (want_merge ? (size_t)(nw > 8 ? 8 : 4) * nv * 64 * 8 : 0);
+    size_t shmem = (size_t)(DP / 2) * 64 * 16 + (size_t)nw * 64 * 8 * (logw2 ? 2 : 1) +
+                   (want_merge ? (size_t)(nw > 8 ? 8 : 4) * nv * 64 * 8 : 0);
     float* lp_k = lp;
     float* grad_k = grad;
     float* lp2_k = lp2;
