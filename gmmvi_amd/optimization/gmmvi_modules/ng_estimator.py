@@ -83,7 +83,8 @@ class SteinNgEstimator(NgEstimator):
 class MoreNgEstimator(NgEstimator):
     """ng_estimator.py:266-376 (MORE, codename letter "Z"): importance-weighted quadratic ridge regression of the
     rewards on the samples whitened by each component (least_squares.py:126-191), as one f32-MFMA Gram contraction
-    and one fp64 Cholesky solve per component (csrc/more.hip): register-resident up to D = 21, tiled above (D <= 63; components of a blocked-path dimension are re-packed for the call)."""
+    and one fp64 Cholesky solve per component (csrc/more.hip): register-resident up to D = 21, tiled above (D <= 63; components of a blocked-path dimension are re-packed for the call).  64 <= D <= 128: csrc/more_blocked.hip
+    (whitening from the dense L^-1 of the blocked component blocks, Cholesky spread over the chip)."""
 
     def __init__(self, temperature, model, only_use_own_samples: bool, initial_l2_regularizer: float,
                  use_self_normalized_importance_weights: bool):
@@ -96,8 +97,11 @@ class MoreNgEstimator(NgEstimator):
             raise ValueError("MoreNgEstimator needs a full-covariance model (the reference's QuadFunc whitening, "
                              "least_squares.py:126-191, has no diagonal branch)")
         from ... import _lib
-        if model.num_dimensions >= _lib.MAX_DIM:
-            raise ValueError(f"MoreNgEstimator: the HIP kernels support D <= {_lib.MAX_DIM - 1} (DESIGN.md section 7)")
+        d = model.num_dimensions
+        self._blocked_route = _lib.MORE_BLOCKED_MIN_DIM <= d <= _lib.MORE_BLOCKED_MAX_DIM and d > _lib.blocked_above()
+        if d >= _lib.MAX_DIM and not self._blocked_route:
+            raise ValueError(f"MoreNgEstimator: the HIP kernels support D <= {_lib.MORE_BLOCKED_MAX_DIM} "
+                             "(DESIGN.md section 7)")
         self.last_model_densities = None
 
     def get_expected_hessian_and_grad(self, samples, mapping, background_densities, target_lnpdfs,
@@ -117,7 +121,7 @@ class MoreNgEstimator(NgEstimator):
             host = getattr(m, "_mapping_max_hint", None)
             mx = int(host) if host is not None else int(np.asarray(map_dev.numpy()).max())
             map_offset = k - 1 - mx                                                        # :342
-        return hip_ops.more(ctx, m.packed, m.chol_cov, x, ld, model_densities, bg, tlp, m.l2_regularizers, d,
-                            mapping=map_dev, map_offset=map_offset,
-                            self_normalized=self._use_self_normalized_importance_weights,
-                            own_samples_only=self._only_use_own_samples)
+        more = hip_ops.more_blocked if self._blocked_route else hip_ops.more
+        return more(ctx, m.packed, m.chol_cov, x, ld, model_densities, bg, tlp, m.l2_regularizers, d,
+                    mapping=map_dev, map_offset=map_offset, self_normalized=self._use_self_normalized_importance_weights,
+                    own_samples_only=self._only_use_own_samples)

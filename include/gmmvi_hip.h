@@ -56,6 +56,7 @@ enum gmmvi_stein_flags {
 #define GMMVI_MORE_REGISTER_MAX_DIM 21  /* gmmvi_more: up to here the F x F ridge system (F = D(D+1)/2 + D + 1) is factorised in
                                          * one workgroup's registers; above (D <= 63; components of a blocked-path dimension are re-packed for the call) a tiled Gram launch and a blocked fp64
                                          * Cholesky in global memory take over */
+#define GMMVI_MORE_BLOCKED_MAX_DIM 128 /* gmmvi_more_blocked: 64 <= D <= 128 from the blocked component layout */
 #define GMMVI_MAX_DIM 64       /* register-resident kernels exist for D <= 64; they are used for D <= 50 (environment
                                 * GMMVI_BLOCKED_ABOVE, 16..64, moves that threshold) */
 #define GMMVI_MAX_DIM_BLOCKED 512   /* above the threshold, D <= 512: blocked kernels (dense L^-1 blocks, fp32 MFMA contractions)
@@ -274,6 +275,19 @@ int gmmvi_more(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const floa
                const float* ld_dev, const float* logq_dev, const float* bg_dev, const float* tlp_dev,
                const int32_t* mapping_dev, int map_offset, int flags, const float* l2_dev, float* H_neg_out_dev,
                float* g_neg_out_dev);
+
+/* The same estimate for 64 <= D <= GMMVI_MORE_BLOCKED_MAX_DIM (= 128): same arguments, flags and outputs as gmmvi_more, with
+ * packed_dev in the blocked layout [mu | log-normaliser | pad | dense L^-1] (stride gmmvi_packed_stride(D)).  The samples
+ * are whitened, and the estimate un-whitened, with the dense L^-1 of the blocks; chols_dev must be given and is not read.
+ * The (F + 1)^2 fp64 Gram matrices (F = D(D+1)/2 + D + 1: 563 MB per component at D = 128) live in the context's
+ * workspace; the components are processed in groups whose workspace stays under 8 GiB (environment GMMVI_MORE_WS_GB,
+ * read per call, at least one component per group) with results that do not depend on the group size.
+ * D outside 64 ... 128 (or D = 64 while GMMVI_BLOCKED_ABOVE = 64 keeps it on the register path) or a missing pointer:
+ * GMMVI_ERR_ARG before any launch; a workspace the device cannot provide: GMMVI_ERR_HIP. */
+int gmmvi_more_blocked(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const float* chols_dev, const float* X_dev,
+                       int N, const float* ld_dev, const float* logq_dev, const float* bg_dev, const float* tlp_dev,
+                       const int32_t* mapping_dev, int map_offset, int flags, const float* l2_dev, float* H_neg_out_dev,
+                       float* g_neg_out_dev);
 
 /* ---- component updates --------------------------------------------------------------------------------------- */
 /* KLConstrainedNgBasedComponentUpdater.apply_NG_update (gmmvi_modules/ng_based_component_updater.py:431-524,
