@@ -13,6 +13,8 @@ SELF_NORMALIZED, OWN_SAMPLES_ONLY, EXPLICIT_ESTIMATE = 1, 2, 4
 MAX_DIM = 64
 MORE_REGISTER_MAX_DIM = 21     # gmmvi_more: register-resident ridge system up to here, the tiled route above (D <= 63)
 MORE_BLOCKED_MIN_DIM, MORE_BLOCKED_MAX_DIM = 64, 128   # gmmvi_more_blocked: MORE from the blocked component layout
+MAX_DIM_BLOCKED = 512          # dense [K, D, D] factors (blocked kernels) exist up to here
+MAX_DIM_DIAG = 131072          # diagonal-covariance mixtures: csrc/diag_sweep.hip, csrc/diag.hip
 BLOCKED_ABOVE_DEFAULT = 50     # csrc/blocked.h: D > 50 runs the blocked (MFMA) kernels
 
 

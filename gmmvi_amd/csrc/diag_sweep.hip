@@ -9,6 +9,10 @@
 // Mapping: lane = sample; the block is wave-uniform, read through a constant-address-space pointer in pieces of 32 dimensions
 // (scalar registers feeding v_sub / v_mul / v_fma); a wave walks a strided subset of the components; the lane keeps its x
 // row in registers when D <= 32 and re-reads 32-dimension pieces of it (L1 / L2 hits) otherwise.
+// D > GMMVI_MAX_DIM_BLOCKED (up to GMMVI_MAX_DIM_DIAG): a log density is of size ~D, so the sums that form it go through fp64 at
+// their second level -- sum log sigma per lane in diag_pack_hd_kernel, the 32-dimension partial sums of the quadratic form in
+// diag_eval_kernel<true> -- and the error stays near one fp32 ulp of the result at every D.  D <= GMMVI_MAX_DIM_BLOCKED keeps the
+// fp32 sums, bit for bit.
 #include "common.h"
 #include "combine.h"
 #include "philox.h"
@@ -43,6 +47,31 @@ __global__ __launch_bounds__(64) void diag_pack_kernel(int D, const float* __res
     }
 }
 
+// the same block for D > GMMVI_MAX_DIM_BLOCKED: 256 threads per component, sum log sigma and the normaliser in fp64
+__global__ __launch_bounds__(256) void diag_pack_hd_kernel(int D, const float* __restrict__ means, const float* __restrict__ sigma,
+                                                           float* __restrict__ packed) {
+    __shared__ double part[4];
+    const int k = blockIdx.x, t = threadIdx.x;
+    float* out = packed + (size_t)k * ds_stride(D);
+    double lsum = 0.0;
+    for (int i = t; i < D; i += 256) {
+        const float sg = sigma[(size_t)k * D + i];
+        out[i] = means[(size_t)k * D + i];
+        out[D + i] = 1.f / sg;
+        out[2 * D + i] = 1.f / (sg * sg);
+        lsum += (double)logf(sg);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
+    if ((t & 63) == 0) part[t >> 6] = lsum;
+    __syncthreads();
+    if (t == 0) {
+        const double total = (part[0] + part[1]) + (part[2] + part[3]);
+        out[3 * D] = (float)(-total - 0.5 * D * 1.8378770664093453);          // - sum log sigma - D/2 log(2 pi)
+        for (int i = 3 * D + 1; i < ds_stride(D); ++i) out[i] = 0.f;
+    }
+}
+
 // one 32-dimension piece of the lane's sample row (dimensions beyond D read as 0)
 __device__ __forceinline__ void ds_load_x(const float* __restrict__ xrow, int d0, int D, bool vec4, float (&x)[DS_CH]) {
     if (vec4 && d0 + DS_CH <= D) {
@@ -60,6 +89,8 @@ __device__ __forceinline__ void ds_load_x(const float* __restrict__ xrow, int d0
 // ---- densities + (dual) log-sum-exp -------------------------------------------------------------------------------------
 // grid (64-sample tiles, component chunks); W waves per workgroup, wave w takes the components k_lo + w, k_lo + w + W, ...
 // ld_out[K, N] (may be NULL), per-chunk log values lp_out[chunk][N] / lp2_out[chunk][N].
+// HD (D > GMMVI_MAX_DIM_BLOCKED): the pieces' partial sums are added in fp64.
+template <bool HD>
 __global__ __launch_bounds__(512) void diag_eval_kernel(int K_total, int D, const float* __restrict__ packed,
                                                         const float* __restrict__ logw, const float* __restrict__ logw2,
                                                         const float* __restrict__ X, int N, float* __restrict__ ld_out,
@@ -84,6 +115,7 @@ __global__ __launch_bounds__(512) void diag_eval_kernel(int K_total, int D, cons
     for (int k = k_lo + wave; k < K; k += nwaves) {
         const ds_cptr blk = (ds_cptr)(uintptr_t)(packed + (size_t)k * stride);
         float q = 0.f;
+        double qd = 0.0;
         for (int d0 = 0; d0 < D; d0 += DS_CH) {
             float x[DS_CH];
             if (one_piece) {
@@ -101,9 +133,10 @@ __global__ __launch_bounds__(512) void diag_eval_kernel(int K_total, int D, cons
                 q0 = d0 + i < D ? fmaf(t0, t0, q0) : q0;
                 q1 = d0 + i + 1 < D ? fmaf(t1, t1, q1) : q1;
             }
-            q += q0 + q1;
+            if (HD) qd += (double)(q0 + q1);
+            else q += q0 + q1;
         }
-        const float ld = fmaf(-0.5f, q, blk[3 * D]);
+        const float ld = HD ? (float)((double)blk[3 * D] - 0.5 * qd) : fmaf(-0.5f, q, blk[3 * D]);
         if (ld_out != nullptr && valid) ld_out[(size_t)k * N + n] = ld;
         const float a = ld + ((ds_cptr)(uintptr_t)logw)[k];
         const float mn = fmaxf(m, a);
@@ -345,11 +378,14 @@ extern "C" {
 size_t gmmvi_diag_packed_stride(int D) { return (size_t)ds_stride(D); }
 
 int gmmvi_diag_pack(gmmvi_ctx* ctx, int K, int D, const float* means_dev, const float* sigma_dev, float* packed_dev) {
-    GMMVI_ARG_CHECK(ctx, K >= 0 && D >= 1 && D <= GMMVI_MAX_DIM_BLOCKED);
+    GMMVI_ARG_CHECK(ctx, K >= 0 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG);
     if (K == 0) return GMMVI_OK;
     GMMVI_ARG_CHECK(ctx, means_dev && sigma_dev && packed_dev);
     GMMVI_PROF(ctx, "diag_pack");
-    hipLaunchKernelGGL(diag_pack_kernel, dim3(K), dim3(64), 0, ctx->stream, D, means_dev, sigma_dev, packed_dev);
+    if (D > GMMVI_MAX_DIM_BLOCKED)
+        hipLaunchKernelGGL(diag_pack_hd_kernel, dim3(K), dim3(256), 0, ctx->stream, D, means_dev, sigma_dev, packed_dev);
+    else
+        hipLaunchKernelGGL(diag_pack_kernel, dim3(K), dim3(64), 0, ctx->stream, D, means_dev, sigma_dev, packed_dev);
     GMMVI_LAUNCH_CHECK(ctx);
     return GMMVI_OK;
 }
@@ -357,7 +393,7 @@ int gmmvi_diag_pack(gmmvi_ctx* ctx, int K, int D, const float* means_dev, const 
 int gmmvi_diag_mixture_eval(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const float* logw_dev, const float* logw2_dev,
                             const float* X_dev, int N, float* ld_out_dev, float* lp_out_dev, float* grad_out_dev,
                             float* lp2_out_dev) {
-    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_BLOCKED && N >= 0);
+    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && N >= 0);
     if (N == 0) return GMMVI_OK;
     GMMVI_ARG_CHECK(ctx, packed_dev && logw_dev && X_dev);
     GMMVI_ARG_CHECK(ctx, ld_out_dev || lp_out_dev || grad_out_dev);
@@ -389,8 +425,12 @@ int gmmvi_diag_mixture_eval(gmmvi_ctx* ctx, int K, int D, const float* packed_de
     float* lp2_k = logw2_dev ? (ky > 1 ? parts + (size_t)ky * N : lp2_out_dev) : nullptr;
     {
         GMMVI_PROF_UNITS(ctx, "diag_sweep", (double)N * K);
-        hipLaunchKernelGGL(diag_eval_kernel, dim3(tiles, ky), dim3(64 * nw), 0, ctx->stream, K, D, packed_dev, logw_dev, logw2_dev,
-                           X_dev, N, ld, need_lp ? lp_k : nullptr, lp2_k);
+        if (D > GMMVI_MAX_DIM_BLOCKED)
+            hipLaunchKernelGGL(diag_eval_kernel<true>, dim3(tiles, ky), dim3(64 * nw), 0, ctx->stream, K, D, packed_dev, logw_dev,
+                               logw2_dev, X_dev, N, ld, need_lp ? lp_k : nullptr, lp2_k);
+        else
+            hipLaunchKernelGGL(diag_eval_kernel<false>, dim3(tiles, ky), dim3(64 * nw), 0, ctx->stream, K, D, packed_dev, logw_dev,
+                               logw2_dev, X_dev, N, ld, need_lp ? lp_k : nullptr, lp2_k);
         GMMVI_LAUNCH_CHECK(ctx);
     }
     if (ky > 1 && (need_lp || logw2_dev)) {
@@ -411,11 +451,12 @@ int gmmvi_diag_mixture_eval(gmmvi_ctx* ctx, int K, int D, const float* packed_de
 int gmmvi_diag_sample(gmmvi_ctx* ctx, int K, int D, const float* means_dev, const float* sigma_dev, const int32_t* offsets_dev,
                       int N, uint64_t seed, uint64_t first_index, int stream_id, const float* eps_dev, float* X_out_dev,
                       int32_t* mapping_out_dev) {
-    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_BLOCKED && N >= 0);
+    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && N >= 0);
     if (N == 0) return GMMVI_OK;
     GMMVI_ARG_CHECK(ctx, means_dev && sigma_dev && offsets_dev && X_out_dev);
     GMMVI_PROF(ctx, "diag_sample");
     const long items = (long)N * ((D + 3) / 4);
+    GMMVI_ARG_CHECK(ctx, items <= 0xFFFFFFFFL - 255);                     // one thread per four values, one launch
     hipLaunchKernelGGL(diag_sample_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, ctx->stream, K, D, means_dev,
                        sigma_dev, offsets_dev, N, seed, first_index, (uint32_t)stream_id, eps_dev, X_out_dev, mapping_out_dev);
     GMMVI_LAUNCH_CHECK(ctx);
@@ -425,7 +466,7 @@ int gmmvi_diag_sample(gmmvi_ctx* ctx, int K, int D, const float* means_dev, cons
 int gmmvi_diag_stein(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const float* X_dev, int N, const float* ld_dev,
                      const float* qgrad_dev, const float* bg_dev, const float* tgrad_dev, const int32_t* mapping_dev,
                      int map_offset, int flags, float* h_neg_diag_out_dev, float* g_neg_out_dev) {
-    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_BLOCKED && N >= 1);
+    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && N >= 1);
     GMMVI_ARG_CHECK(ctx, packed_dev && X_dev && qgrad_dev && tgrad_dev && h_neg_diag_out_dev && g_neg_out_dev);
     if (flags & GMMVI_OWN_SAMPLES_ONLY) GMMVI_ARG_CHECK(ctx, mapping_dev != nullptr);
     else GMMVI_ARG_CHECK(ctx, ld_dev && bg_dev);

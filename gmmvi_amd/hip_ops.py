@@ -315,13 +315,25 @@ def update_components_plain(ctx, mode, means, chols, h_neg, g_neg, stepsizes, l2
 
 
 # ---- dedicated kernels for diagonal mixtures (csrc/diag_sweep.hip): O(D) per (sample, component) pair ----------------------
+def _diag_dim(d, what):
+    if not 1 <= d <= _lib.MAX_DIM_DIAG:
+        raise ValueError(f"{what}: D = {d} is outside the diagonal kernels' range 1 <= D <= {_lib.MAX_DIM_DIAG}")
+
+
+def _dense_dim(d, what):
+    if not 1 <= d <= _lib.MAX_DIM_BLOCKED:
+        raise ValueError(f"{what}: dense [K, D, D] factors exist for 1 <= D <= {_lib.MAX_DIM_BLOCKED} only, got D = {d}")
+
+
 def diag_packed_stride(d):
+    _diag_dim(d, "diag_packed_stride")
     return int(_lib.load().gmmvi_diag_packed_stride(int(d)))
 
 
 def diag_pack(ctx, means, sigma):
     """(means [K,D], standard deviations [K,D]) -> component blocks [K, diag_packed_stride(D)]."""
     k, d = means.shape
+    _diag_dim(d, "diag_pack")
     _req(means, (k, d), name="means"); _req(sigma, (k, d), name="sigma")
     packed = ctx.empty((k, diag_packed_stride(d)))
     ctx.check(ctx.lib.gmmvi_diag_pack(ctx.handle, k, d, means.ptr, sigma.ptr, packed.ptr))
@@ -350,6 +362,7 @@ def diag_mixture_eval(ctx, packed, logw, x, d, want_ld=False, want_lp=True, want
 def diag_sample(ctx, means, sigma, offsets, n, seed=0, first_index=0, stream_id=0, eps=None):
     """x = mu_k + sigma_k * eps in component order -> (x [n,D], mapping [n] int32); arguments as sample_components."""
     k, d = means.shape
+    _diag_dim(d, "diag_sample")
     _req(means, (k, d), name="means"); _req(sigma, (k, d), name="sigma"); _req(offsets, (k + 1,), I32, "offsets")
     if eps is not None:
         _req(eps, (n, d), name="eps")
@@ -385,6 +398,7 @@ def diag_stein(ctx, packed, x, ld, qgrad, bg, tgrad, d, mapping=None, map_offset
 def diag_embed(ctx, chols_diag):
     """[K,D] sigma -> dense lower-triangular factors [K,D,D] = diag(sigma) for the dense density / sampling kernels."""
     k, d = chols_diag.shape
+    _dense_dim(d, "diag_embed")
     _req(chols_diag, (k, d), name="chols_diag")
     dense = ctx.empty((k, d, d))
     ctx.check(ctx.lib.gmmvi_diag_embed(ctx.handle, k, d, chols_diag.ptr, dense.ptr))
@@ -394,6 +408,7 @@ def diag_embed(ctx, chols_diag):
 def diag_extract(ctx, dense):
     """[K,D,D] -> its diagonals [K,D]."""
     k, d, _ = dense.shape
+    _dense_dim(d, "diag_extract")
     _req(dense, (k, d, d), name="dense")
     diag = ctx.empty((k, d))
     ctx.check(ctx.lib.gmmvi_diag_extract(ctx.handle, k, d, dense.ptr, diag.ptr))
@@ -412,6 +427,7 @@ def update_components_diag(ctx, mode, means, chols_diag, h_neg_diag, g_neg, step
                            num_updates, want_info=False):
     """Diagonal-covariance component update, mode "kl" or "iblr" -> (success, kl | None, probes | None)."""
     k, d = means.shape
+    _diag_dim(d, "update_components_diag")
     _req(means, (k, d), name="means"); _req(chols_diag, (k, d), name="chols_diag")
     _req(h_neg_diag, (k, d), name="h_neg_diag"); _req(g_neg, (k, d), name="g_neg")
     _req(stepsizes, (k,), name="stepsizes"); _req(l2, (k,), name="l2"); _req(num_updates, (k,), name="num_updates")

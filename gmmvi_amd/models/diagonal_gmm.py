@@ -2,12 +2,13 @@
 
 ``chol_cov`` is the reference's [K, D] array of standard deviations.  Densities, gradients, the background density and
 sampling run on dedicated O(D)-per-pair kernels (csrc/diag_sweep.hip: component blocks [mu | 1/sigma | 1/sigma^2 | c]); the
-component updates have their own elementwise kernels (csrc/diag.hip).  ``dense_chol`` (the embedded factors diag(sigma)) is
-still available for callers of the dense entry points.
+component updates have their own elementwise kernels (csrc/diag.hip).  All of them take 1 <= D <= _lib.MAX_DIM_DIAG.
+``dense_chol`` (the embedded factors diag(sigma)) is still available for callers of the dense entry points, up to
+D = _lib.MAX_DIM_BLOCKED: above it no [K, D, D] array is ever allocated.
 """
 import numpy as np
 
-from .. import hip_ops
+from .. import _lib, hip_ops
 from ..device import DeviceArray
 from .gmm import GMM
 
@@ -22,6 +23,9 @@ class DiagonalGMM(GMM):
         covs_host = np.asarray(covs.numpy() if hasattr(covs, "numpy") else covs, np.float32)
         if covs_host.ndim != 2 or covs_host.shape != tuple(means.shape):
             raise ValueError(f"covs must be [K,D]; got {covs_host.shape} for means {means.shape}")
+        if covs_host.shape[1] > _lib.MAX_DIM_DIAG:
+            raise ValueError(f"DiagonalGMM: D = {covs_host.shape[1]} is above the diagonal kernels' limit "
+                             f"(D <= {_lib.MAX_DIM_DIAG})")
         if not np.all(covs_host > 0):
             raise ValueError("initial covariance entries must be positive")
         w = np.asarray(weights.numpy() if hasattr(weights, "numpy") else weights, dtype=np.float64)
@@ -38,6 +42,9 @@ class DiagonalGMM(GMM):
 
     @property
     def dense_chol(self):
+        if self.num_dimensions > _lib.MAX_DIM_BLOCKED:
+            raise _lib.GmmviError(f"DiagonalGMM.dense_chol: the dense [K, D, D] factors exist for D <= {_lib.MAX_DIM_BLOCKED} "
+                                  f"only (D = {self.num_dimensions}); use the diagonal entry points")
         if self._dense is None:
             self._dense = hip_ops.diag_embed(self.ctx, self.chol_cov)
         return self._dense

@@ -63,8 +63,9 @@ class NgBasedComponentUpdaterIblr(NgBasedComponentUpdater):
 
 
 class KLConstrainedNgBasedComponentUpdater(NgBasedComponentUpdater):
-    """:226-524: the per-component bracketing search runs on the device, one wavefront per component, with the
-    reference's stop rules; means / Cholesky factors / last etas / l2 regularisers are updated in place."""
+    """:226-524: the per-component bracketing search runs on the device, one wavefront per component (diagonal models above
+    D = 512: one workgroup per component), with the reference's stop rules; means / Cholesky factors / last etas / l2
+    regularisers are updated in place."""
 
     def apply_NG_update(self, expected_hessians_neg, expected_gradients_neg, stepsizes):
         m = self.model

@@ -12,7 +12,7 @@ import os
 
 import numpy as np
 
-from .. import hip_ops
+from .. import _lib, hip_ops
 from ..device import DeviceArray, get_context
 
 
@@ -291,6 +291,9 @@ class SampleDB:
         if chols.ndim == 2:
             if not self.diagonal_covariances:
                 raise ValueError("SampleDB(diagonal_covariances=False) got [K,D] Cholesky factors")
+            if chols.shape[1] > _lib.MAX_DIM_BLOCKED:
+                raise _lib.GmmviError(f"SampleDB: dense [K, D, D] factors exist for D <= {_lib.MAX_DIM_BLOCKED} only "
+                                      f"(D = {chols.shape[1]})")
             return hip_ops.diag_embed(self.ctx, chols)
         if self.diagonal_covariances:
             raise ValueError("SampleDB(diagonal_covariances=True) got [K,D,D] Cholesky factors")

@@ -62,6 +62,10 @@ enum gmmvi_stein_flags {
 #define GMMVI_MAX_DIM_BLOCKED 512   /* above the threshold, D <= 512: blocked kernels (dense L^-1 blocks, fp32 MFMA contractions)
                                      * behind gmmvi_packed_stride / pack_components / cholesky / mixture_eval(_dual) /
                                      * sample_components / stein / update_components_kl / _direct / _iblr */
+#define GMMVI_MAX_DIM_DIAG 131072   /* diagonal-covariance mixtures, 1 <= D <= 131072: the O(D) kernels of csrc/diag_sweep.hip and the
+                                     * component updates of csrc/diag.hip (one wavefront per component up to GMMVI_MAX_DIM_BLOCKED, one
+                                     * workgroup per component above).  gmmvi_diag_embed / _extract build [K,D,D] and stay at
+                                     * GMMVI_MAX_DIM_BLOCKED */
 
 /* ---- context, errors, memory ------------------------------------------------------------------------ */
 int gmmvi_device_count(void);
@@ -509,7 +513,8 @@ int gmmvi_combine_partials(gmmvi_ctx* ctx, int R, int N, int D, const float* lp_
  * uses the dedicated kernels below since round 3):
  * gmmvi_diag_embed writes dense[K,D,D] from diag[K,D]; gmmvi_diag_extract reads diag[K,D] = diagonal of dense[K,D,D]
  * (the diagonal Stein estimate of gmmvi_modules/ng_estimator.py:159-162,:178-181 is the diagonal of gmmvi_stein's
- * H_neg); gmmvi_reciprocal_f32 is SampleDB's inv_chols = 1 / chols (optimization/sample_db.py:119,:130). */
+ * H_neg), both for D <= GMMVI_MAX_DIM_BLOCKED; gmmvi_reciprocal_f32 is SampleDB's inv_chols = 1 / chols
+ * (optimization/sample_db.py:119,:130), any length. */
 int gmmvi_diag_embed(gmmvi_ctx* ctx, int K, int D, const float* diag_dev, float* dense_out_dev);
 int gmmvi_diag_extract(gmmvi_ctx* ctx, int K, int D, const float* dense_dev, float* diag_out_dev);
 int gmmvi_reciprocal_f32(gmmvi_ctx* ctx, const float* src_dev, size_t n, float* dst_dev);
@@ -521,7 +526,10 @@ int gmmvi_reciprocal_f32(gmmvi_ctx* ctx, const float* src_dev, size_t n, float* 
  *   gmmvi_diag_sample        GMM.sample_from_components_no_shuffle for a DiagonalGMM (x = mu + sigma * eps,
  *                            models/diagonal_gmm.py:43-45): same offsets / Philox arguments as gmmvi_sample_components
  *   gmmvi_diag_stein         SteinNgEstimator, diagonal branches (ng_estimator.py:159-162,:178-181): h_neg_diag[K,D], g_neg[K,D];
- *                            arguments as gmmvi_stein */
+ *                            arguments as gmmvi_stein
+ * All four and gmmvi_diag_pack take 1 <= D <= GMMVI_MAX_DIM_DIAG.  Above GMMVI_MAX_DIM_BLOCKED the log-normaliser and the quadratic
+ * form are accumulated in fp64 over the 32-dimension pieces (a log density is of size ~D there: its error stays near one fp32
+ * ulp of the result at every D); up to GMMVI_MAX_DIM_BLOCKED the results are those of the fp32 sums, bit for bit. */
 size_t gmmvi_diag_packed_stride(int D);
 int gmmvi_diag_pack(gmmvi_ctx* ctx, int K, int D, const float* means_dev, const float* sigma_dev, float* packed_out_dev);
 int gmmvi_diag_mixture_eval(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const float* logw_dev, const float* logw2_dev,
@@ -536,14 +544,17 @@ int gmmvi_diag_stein(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, cons
 
 /* KLConstrainedNgBasedComponentUpdater.apply_NG_update, diagonal branches (gmmvi_modules/
  * ng_based_component_updater.py:447-453, kl() :304-318, :483-490); same contract as gmmvi_update_components_kl with
- * chols[K,D] and H_neg[K,D].  D <= GMMVI_MAX_DIM_BLOCKED. */
+ * chols[K,D] and H_neg[K,D].  1 <= D <= GMMVI_MAX_DIM_DIAG: up to GMMVI_MAX_DIM_BLOCKED one wavefront per component with the
+ * component in registers; above, one workgroup per component with the per-dimension state in LDS (D <= 8192) or re-read from
+ * global memory, the KL summed as the per-dimension terms log r + 1/r - 1 (r = new precision / precision).  Same stop
+ * rules and outputs on both routes. */
 int gmmvi_update_components_diag_kl(gmmvi_ctx* ctx, int K, int D, float* means_dev, float* chols_diag_dev,
                                     const float* H_neg_diag_dev, const float* g_neg_dev, const float* stepsizes_dev,
                                     float temperature, float l2_init, float* last_eta_dev, float* l2_dev,
                                     float* num_received_updates_dev, int32_t* success_out_dev, float* kl_out_dev,
                                     int32_t* n_probes_out_dev);
 /* NgBasedComponentUpdaterIblr, diagonal branches (:170-174, :188-189, :195-197).  (The reference's direct updater
- * has no diagonal branch.) */
+ * has no diagonal branch.)  1 <= D <= GMMVI_MAX_DIM_DIAG, routes as gmmvi_update_components_diag_kl. */
 int gmmvi_update_components_diag_iblr(gmmvi_ctx* ctx, int K, int D, float* means_dev, float* chols_diag_dev,
                                       const float* H_neg_diag_dev, const float* g_neg_dev, const float* stepsizes_dev,
                                       float l2_init, float* l2_dev, float* num_received_updates_dev,
