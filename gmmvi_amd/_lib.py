@@ -100,6 +100,8 @@ _PROTOS = {
     "gmmvi_target_logreg_mb": (_i, [_p, _i, _i, _p, _i, _i, _u64, _u32, _f, _f, _p, _i, _p, _p]),
     "gmmvi_target_bnn": (_i, [_p, _i, _i, _i, _i, _p, _p, _u64, _u32, _i, _f, _f, _p, _i, _p, _p]),
     "gmmvi_bnn_predict": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p]),
+    "gmmvi_target_bnn_classifier": (_i, [_p, _i, _i, _i, _i, _p, _p, _u64, _u32, _i, _f, _f, _p, _i, _p, _p]),
+    "gmmvi_bnn_classifier_predict": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p]),
     "gmmvi_target_talos": (_i, [_p, _p, _p, _p, _i, _p, _p]),
     "gmmvi_talos_fk": (_i, [_p, _p, _p, _i, _p, _p]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),

@@ -56,8 +56,9 @@ def _lookup_target(experiment):
 def get_target_lnpdf(experiment, environment_config, seed):
     """:46-86.  In scope here: PlanarRobot1/4, STM, GMM*, DIAGGMM*, breastCancer(_mb), GermanCredit(_mb), WINE*, Talos*
     (``environment_config`` may name the ``dataset_dir``; WINE takes ``seed`` as its dataset seed and as the seed of its
-    minibatch stream, the _mb variants as the seed of theirs; Talos takes the left gripper's goal as ``context``); the
-    reference's other benchmark posterior (MNIST) plugs in as ``config['target_fn']`` through the LNPDF interface."""
+    minibatch stream, the _mb variants as the seed of theirs; Talos takes the left gripper's goal as ``context``).  The
+    MNIST posterior has no name here: build it with ``target_distributions.bnn.make_MNIST_target(...)`` and pass it as
+    ``config['target_fn']``, like any other LNPDF."""
     missing = [k for k in _REQUIRED_CONFIG.get(experiment, ()) if k not in environment_config]
     if missing:
         raise ValueError(f"get_target_lnpdf(): the minibatch variant {experiment} needs {', '.join(missing)} in "

@@ -222,3 +222,163 @@ class BNN_WINE(BNNRegression):
 def make_WINE_target(likelihood_scaling, dataset_seed, prior_std, batch_size, dataset_dir=None, seed=None):
     return BNN_WINE(dataset_seed=dataset_seed, likelihood_scaling=likelihood_scaling, prior_std=prior_std,
                     batch_size=batch_size, dataset_dir=dataset_dir, seed=seed)
+
+
+# ---- classification: features -> H (ReLU) -> C logits under a cross-entropy likelihood (BNN_MNIST) -----------------------
+MAX_CLASSIFIER_FEATURES, MAX_CLASSIFIER_HIDDEN = 1024, 128     # what csrc/bnn_classifier.hip supports
+MIN_CLASSES, MAX_CLASSES, MAX_CLASSIFIER_BATCH = 2, 16, 1024
+MNIST_FILE = os.path.join("mnist", "mnist.npz")
+MNIST_ARRAYS = ("x_train", "y_train", "x_test", "y_test")
+MNIST_TEST_ROWS = 5000                                         # bnn.py:336: ds_test.take(5000) / ds_test.skip(5000)
+
+
+def classifier_num_parameters(num_features, hidden, num_classes):
+    """W1 [F, H], b1 [H], W2 [H, C], b2 [C]: 101 770 for MNIST's (784, 128, 10)."""
+    return hip_ops.bnn_classifier_num_parameters(num_features, hidden, num_classes)
+
+
+class BNNClassification(LNPDF):
+    """Posterior of a features -> H (ReLU) -> C (logits) network with the sparse categorical cross-entropy from logits on
+    minibatches of ``batch_size`` rows and a zero-mean normal prior of standard deviation ``prior_std`` (bnn.py:59-240
+    with the network and loss of BNN_MNIST, bnn.py:312-351):
+        log p(w) = s (-T mean_m (logsumexp(l_m) - l_m[y_m]) - 0.5 sum_d w_d^2 / sd^2).
+
+    ``features`` [T, F] and integer ``labels`` [T] in [0, num_classes) are the training set; ``eval_sets`` maps "test" /
+    "vali" to (features, labels) pairs for ``expensive_metrics``.  The minibatch stream, its ``seed`` and ``call_count``
+    are BNNRegression's."""
+
+    def __init__(self, features, labels, num_classes, hidden_units=(128,), likelihood_scaling=1., prior_std=1.,
+                 batch_size=128, seed=0, eval_sets=None):
+        super().__init__(use_log_density_and_grad=True)
+        X = np.asarray(features, np.float32)
+        y = np.asarray(labels)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError(f"features must be [T, F] and labels [T], got {X.shape} and {y.shape}")
+        hidden_units = tuple(int(h) for h in hidden_units)
+        if len(hidden_units) != 1:
+            raise ValueError(f"hidden_units must name one hidden layer, got {hidden_units}")
+        if not 1 <= X.shape[1] <= MAX_CLASSIFIER_FEATURES:
+            raise ValueError(f"the network takes 1 to {MAX_CLASSIFIER_FEATURES} features, got {X.shape[1]}")
+        if not 1 <= hidden_units[0] <= MAX_CLASSIFIER_HIDDEN:
+            raise ValueError(f"the hidden layer must have 1 to {MAX_CLASSIFIER_HIDDEN} units, got {hidden_units[0]}")
+        if not MIN_CLASSES <= int(num_classes) <= MAX_CLASSES:
+            raise ValueError(f"num_classes must lie in [{MIN_CLASSES}, {MAX_CLASSES}], got {num_classes}")
+        if not 1 <= int(batch_size) <= min(X.shape[0], MAX_CLASSIFIER_BATCH):
+            raise ValueError(f"batch_size must lie in [1, {min(X.shape[0], MAX_CLASSIFIER_BATCH)}] (the training-set size, "
+                             f"at most {MAX_CLASSIFIER_BATCH}), got {batch_size}")
+        if not prior_std > 0:
+            raise ValueError("prior_std must be positive")
+        if y.size and (not np.all(y == np.floor(y)) or y.min() < 0 or y.max() >= int(num_classes)):
+            raise ValueError(f"labels must be integers in [0, {int(num_classes)}) (num_classes), got values in "
+                             f"[{y.min()}, {y.max()}]")
+        self.features, self.labels = X, y.astype(np.int32)
+        self.num_classes, self.hidden_units = int(num_classes), hidden_units
+        self.likelihood_scaling, self.prior_std = float(likelihood_scaling), float(prior_std)
+        self.batch_size, self.seed = int(batch_size), int(seed)
+        self.eval_sets = {k: (np.asarray(f, np.float32), np.asarray(l).astype(np.int32))
+                          for k, (f, l) in (eval_sets or {}).items()}
+        self._call = 0
+        self.ctx = get_context()
+        self._X_dev, self._y_dev = self.ctx.asarray(X), self.ctx.asarray(self.labels, np.int32)
+
+    @property
+    def call_count(self):
+        return self._call
+
+    @property
+    def train_size(self):
+        return int(self.features.shape[0])
+
+    def get_num_dimensions(self):
+        return classifier_num_parameters(self.features.shape[1], self.hidden_units[0], self.num_classes)
+
+    def _evaluate(self, x, want_grad):
+        x = self.ctx.asarray(x)
+        lp, grad = hip_ops.target_bnn_classifier(self.ctx, self._X_dev, self._y_dev, self.hidden_units[0], self.num_classes,
+                                                 self.seed, self._call, self.batch_size, self.likelihood_scaling,
+                                                 self.prior_std, x, want_grad=want_grad)
+        if x.shape[0] >= 1:
+            self._call += 1
+        return lp, grad
+
+    def log_density(self, x):
+        return self._evaluate(x, False)[0]
+
+    def log_density_and_grad(self, x):
+        return self._evaluate(x, True)
+
+    def predict(self, samples, features):
+        """Logits [S, M, C] of the weight vectors ``samples`` [S, D] on the rows ``features`` [M, F]."""
+        return hip_ops.bnn_classifier_predict(self.ctx, self.hidden_units[0], self.num_classes, self.ctx.asarray(samples),
+                                              self.ctx.asarray(np.asarray(features, np.float32)))
+
+    def bayesian_inference_loss(self, samples, dataset):
+        """bnn.py:290-310: the logits averaged over the samples, then the cross-entropy from logits and the sparse
+        categorical accuracy of every batch of ``batch_size`` rows (stored order, the last batch partial), averaged over
+        the batches in fp64 -> (loss, accuracy)."""
+        features, labels = self.eval_sets[dataset]
+        out = self.predict(samples, features)
+        logits = (out.numpy() if hasattr(out, "numpy") else np.asarray(out)).astype(np.float64).mean(0)
+        losses, accuracies = [], []
+        for b0 in range(0, len(labels), self.batch_size):
+            l, y = logits[b0:b0 + self.batch_size], labels[b0:b0 + self.batch_size]
+            mx = l.max(1)
+            lse = mx + np.log(np.exp(l - mx[:, None]).sum(1))
+            losses.append(np.mean(lse - l[np.arange(len(y)), y]))
+            accuracies.append(np.mean(l.argmax(1) == y))
+        return float(np.mean(losses)), float(np.mean(accuracies))
+
+    def expensive_metrics(self, model, samples) -> dict:
+        """bnn.py:353-380, keys as BNN_MNIST names them."""
+        metrics = dict()
+        if "test" in self.eval_sets:
+            loss, accuracy = self.bayesian_inference_loss(samples, "test")
+            metrics.update({"bi_test_loss": loss, "bi_test_accuracy": accuracy})
+        if "vali" in self.eval_sets:
+            loss, accuracy = self.bayesian_inference_loss(samples, "vali")
+            metrics.update({"bi_vali_loss": loss, "bi_vali_accuracy": accuracy})
+        return metrics
+
+
+def load_mnist(dataset_dir=None):
+    """MNIST from ``mnist/mnist.npz`` below the dataset directory, in the widely mirrored array layout: ``x_train`` uint8
+    [60000, 28, 28], ``y_train`` [60000], ``x_test`` [10000, 28, 28], ``y_test``.  Features are uint8 / 255 in f32
+    (bnn.py:329-331), flattened to 784; "test" is the first 5 000 test rows and "vali" the rest (bnn.py:336).  A file of
+    the same layout with at most 5 000 test rows is split in halves.  Upstream reads the TFDS copy with shuffled files,
+    so its row order is not reproducible; the rows here keep the file's order."""
+    d = dataset_dir if dataset_dir is not None else os.environ.get(DATASET_DIR_ENV)
+    if not d:
+        raise FileNotFoundError(
+            f"no dataset directory for the MNIST target: pass dataset_dir or set the {DATASET_DIR_ENV} environment "
+            f"variable to a directory holding {MNIST_FILE}")
+    path = os.path.join(d, MNIST_FILE)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path} does not exist: the dataset directory (dataset_dir or {DATASET_DIR_ENV}) must "
+                                f"hold {MNIST_FILE} with the arrays {', '.join(MNIST_ARRAYS)}")
+    with np.load(path, allow_pickle=False) as z:
+        raw = {k: z[k] for k in MNIST_ARRAYS}
+
+    def images(a):
+        return (a.reshape(a.shape[0], -1).astype(np.float32) / np.float32(255.)).astype(np.float32)
+
+    x_test, y_test = images(raw["x_test"]), raw["y_test"].astype(np.int32)
+    cut = MNIST_TEST_ROWS if x_test.shape[0] > MNIST_TEST_ROWS else x_test.shape[0] // 2
+    return {"features_train": images(raw["x_train"]), "labels_train": raw["y_train"].astype(np.int32),
+            "features_test": x_test[:cut], "labels_test": y_test[:cut],
+            "features_vali": x_test[cut:], "labels_vali": y_test[cut:]}
+
+
+class BNN_MNIST(BNNClassification):
+    """bnn.py:312-380: 784 -> 128 (ReLU) -> 10 on MNIST, D = 101 770; ``seed`` keys the minibatch stream."""
+
+    def __init__(self, likelihood_scaling, prior_std, batch_size, dataset_dir=None, seed=0):
+        data = load_mnist(dataset_dir)
+        super().__init__(data["features_train"], data["labels_train"], num_classes=10, hidden_units=(128,),
+                         likelihood_scaling=likelihood_scaling, prior_std=prior_std, batch_size=batch_size, seed=seed,
+                         eval_sets={"test": (data["features_test"], data["labels_test"]),
+                                    "vali": (data["features_vali"], data["labels_vali"])})
+
+
+def make_MNIST_target(likelihood_scaling, prior_std, batch_size, dataset_dir=None, seed=0):
+    return BNN_MNIST(likelihood_scaling=likelihood_scaling, prior_std=prior_std, batch_size=batch_size,
+                     dataset_dir=dataset_dir, seed=seed)

@@ -153,6 +153,48 @@ def bnn_predict(ctx, hidden_units, W, X):
     return out
 
 
+def bnn_classifier_num_parameters(num_features, hidden, num_classes):
+    f, h, c = int(num_features), int(hidden), int(num_classes)
+    return f * h + h + h * c + c
+
+
+def target_bnn_classifier(ctx, X, labels, hidden, num_classes, seed, call, batch_size, likelihood_scaling, prior_std, x,
+                          want_grad=True):
+    """Bayesian-neural-network classification posterior (csrc/bnn_classifier.hip).  X: [T, F] training features, labels:
+    [T] int32 in [0, num_classes), one ReLU layer of ``hidden`` units; the minibatch rows come from the stream of
+    (seed, call).  -> (lp [n], grad [n, D])."""
+    t, f = X.shape
+    h, c = int(hidden), int(num_classes)
+    d = bnn_classifier_num_parameters(f, h, c)
+    n = x.shape[0]
+    _req(X, (t, f), name="X"); _req(labels, (t,), I32, name="labels"); _req(x, (n, d), name="x")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_bnn_classifier(ctx.handle, f, h, c, t, X.ptr, labels.ptr,
+                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF,
+                                                      int(batch_size), float(likelihood_scaling), float(prior_std), x.ptr,
+                                                      n, lp.ptr, None if grad is None else grad.ptr))
+    return lp, grad
+
+
+def bnn_classifier_predict(ctx, hidden, num_classes, W, X):
+    """Logits of every weight vector on every row (csrc/bnn_classifier.hip), forward only.  W: [S, D], X: [M, F]
+    -> [S, M, C]."""
+    m, f = X.shape
+    h, c = int(hidden), int(num_classes)
+    d = bnn_classifier_num_parameters(f, h, c)
+    s = W.shape[0]
+    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
+    out = ctx.empty((s, m, c))
+    if m > 0:
+        for s0 in range(0, s, 65535):                   # the kernel's grid takes at most 65535 weight vectors per launch
+            s1 = min(s, s0 + 65535)
+            ctx.check(ctx.lib.gmmvi_bnn_classifier_predict(ctx.handle, f, h, c, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m,
+                                                           out.rows(s0, s1).ptr))
+    return out
+
+
 TALOS_DIM = 34                                          # csrc/talos.hip: 28 joints, base position, roll / pitch / yaw
 TALOS_TABLE_SIZE = 8 + 28 * 28 + 4 * 16                 # header, joint records, tip records (talos_ik.py)
 

@@ -228,6 +228,24 @@ int gmmvi_target_bnn(gmmvi_ctx* ctx, int F, int H1, int H2, int T, const float* 
 int gmmvi_bnn_predict(gmmvi_ctx* ctx, int F, int H1, int H2, const float* W_dev, int S, const float* X_dev, int M,
                       float* out_dev);
 
+/* Bayesian-neural-network classification (target_distributions/bnn.py, BNN_LNPDF with the network and loss of BNN_MNIST)
+ * and its analytic gradient.  Network F -> H (ReLU) -> C (logits); W_dev[N,D] in the reference's layout W1 [F,H] row-major,
+ * b1 [H], W2 [H,C] row-major, b2 [C], so D = F H + H + H C + C.  X_dev[T,F] f32, labels_dev[T] int32 in [0, C): the
+ * training set.  Sample n sees the B rows of gmmvi_target_bnn's minibatch stream (stream id 3) for (seed, call):
+ *   lp[n]   = likelihood_scaling (-(T/B) sum_j (logsumexp(l_j) - l_j[y_j]) - 0.5 sum_d w_nd^2 / prior_std^2)
+ *   grad[n] = d lp[n] / d w_n      (ReLU derivative 1 where the pre-activation is positive, else 0)
+ * grad_out_dev may be NULL (lp is bitwise the same); N == 0 launches nothing.  1 <= F <= 1024, 1 <= H <= 128,
+ * 2 <= C <= 16, 1 <= B <= min(T, 1024), prior_std > 0; anything else: GMMVI_ERR_ARG.  A label outside [0, C) selects no
+ * logit (the caller checks the labels).  Bitwise reproducible for a given (seed, call): no atomics. */
+int gmmvi_target_bnn_classifier(gmmvi_ctx* ctx, int F, int H, int C, int T, const float* X_dev, const int32_t* labels_dev,
+                                uint64_t seed, uint32_t call, int B, float likelihood_scaling, float prior_std,
+                                const float* W_dev, int N, float* lp_out_dev, float* grad_out_dev);
+
+/* The same network's logits, forward only: logits[s, m, c] of X[m] under W[s].  W_dev[S,D], X_dev[M,F],
+ * logits_out_dev[S,M,C]; S <= 65535; S == 0 or M == 0 launches nothing. */
+int gmmvi_bnn_classifier_predict(gmmvi_ctx* ctx, int F, int H, int C, const float* W_dev, int S, const float* X_dev, int M,
+                                 float* logits_out_dev);
+
 /* Talos humanoid inverse kinematics (target_distributions/talos_ik.py; DESIGN.md 6, "Talos (defined, not reproduced)") and
  * its analytic gradient.  model_dev: the packed f32 table of talos_ik.TalosModel (28 revolute joints, 4 tips, lumped
  * masses); context_dev[3]: the left gripper's goal.  X_dev[N,34] = [q (28), p_b (3), roll, pitch, yaw]:
