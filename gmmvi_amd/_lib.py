@@ -115,6 +115,7 @@ _PROTOS = {
     "gmmvi_update_components_direct": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p]),
     "gmmvi_update_components_iblr": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p]),
     "gmmvi_expected_log_ratios": (_i, [_p, _i, _i, _p, _p, _p, _p, _f, _p, _i, _p, _p, _p]),
+    "gmmvi_expected_log_ratios_parts": (_i, [_p, _i, _i, _p, _p, _p, _p, _i, _f, _p, _i, _p, _p, _p]),
     "gmmvi_update_weights_kl": (_i, [_p, _i, _p, _p, _p, _f, _p]),
     "gmmvi_update_weights_direct": (_i, [_p, _i, _p, _p, _p, _f]),
     "gmmvi_component_stepsize_improvement": (_i, [_p, _i, _p, _p, _p, _f, _f, _f, _f]),

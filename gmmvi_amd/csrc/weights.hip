@@ -254,7 +254,10 @@ __global__ __launch_bounds__(64) void update_weights_kernel(int mode, int K, flo
     const int t = threadIdx.x;
     for (int i = t; i < K; i += 64) { lw[i] = logw[i]; E[i] = E_in[i]; nl[i] = logw[i]; }
     __syncthreads();
-    if (K <= 1) return;                                                                   // :136 / :275
+    if (K <= 1) {                                                                         // :136 / :275: no update, (kl, eta) = (-1, -1)
+        if (t == 0 && kl_eta_out) { kl_eta_out[0] = -1.f; kl_eta_out[1] = -1.f; }
+        return;
+    }
     const float bound = stepsize[0];
     float kl = -1.f, eta = -1.f;
     bool updated = true;
@@ -330,6 +333,27 @@ __global__ __launch_bounds__(64) void weight_stepsize_kernel(int K, const float*
 
 }  // namespace
 
+// the one launch behind both entry points below.  logq_R == 0: logq_dev holds the final log values [N]; logq_R >= 2: the chunk
+// partials [logq_R][N], merged while they are read
+static int elr_launch(gmmvi_ctx* ctx, int K, int N, const float* ld_dev, const float* bg_dev, const float* tlp_dev,
+                      const float* logq_dev, int logq_R, float beta, const float* logw_dev, int self_normalized,
+                      float* E_out_dev, float* reward_out_dev, float* ess_out_dev) {
+    GMMVI_PROF(ctx, "expected_log_ratios");
+    const Riders riders = gmmvi_take_pending_riders(ctx, K, 1024);
+    if (riders.prep_blocks + riders.sample_blocks > 0) {
+        const int dp = gmmvi_padded_dim(riders.sample_blocks > 0 ? riders.sample.D : 2);
+        GMMVI_DISPATCH_DP(dp, hipLaunchKernelGGL((elr_riders_kernel<DP>), dim3(K + riders.prep_blocks + riders.sample_blocks),
+                                                 dim3(1024), riders_lds_bytes(riders), ctx->stream, N, ld_dev, bg_dev, tlp_dev,
+                                                 logq_dev, logq_R, beta, logw_dev, self_normalized, E_out_dev, reward_out_dev,
+                                                 ess_out_dev, riders));
+    } else {
+        hipLaunchKernelGGL(elr_kernel, dim3(K), dim3(1024), 0, ctx->stream, N, ld_dev, bg_dev, tlp_dev, logq_dev, logq_R, beta,
+                           logw_dev, self_normalized, E_out_dev, reward_out_dev, ess_out_dev);
+    }
+    GMMVI_LAUNCH_CHECK(ctx);
+    return GMMVI_OK;
+}
+
 extern "C" {
 
 int gmmvi_expected_log_ratios(gmmvi_ctx* ctx, int K, int N, const float* ld_dev, const float* bg_dev,
@@ -351,20 +375,20 @@ int gmmvi_expected_log_ratios(gmmvi_ctx* ctx, int K, int N, const float* ld_dev,
             if (rc != GMMVI_OK) return rc;
         }
     }
-    GMMVI_PROF(ctx, "expected_log_ratios");
-    const Riders riders = gmmvi_take_pending_riders(ctx, K, 1024);
-    if (riders.prep_blocks + riders.sample_blocks > 0) {
-        const int dp = gmmvi_padded_dim(riders.sample_blocks > 0 ? riders.sample.D : 2);
-        GMMVI_DISPATCH_DP(dp, hipLaunchKernelGGL((elr_riders_kernel<DP>), dim3(K + riders.prep_blocks + riders.sample_blocks),
-                                                 dim3(1024), riders_lds_bytes(riders), ctx->stream, N, ld_dev, bg_dev, tlp_dev,
-                                                 logq_dev, logq_R, beta, logw_dev, self_normalized, E_out_dev, reward_out_dev,
-                                                 ess_out_dev, riders));
-    } else {
-        hipLaunchKernelGGL(elr_kernel, dim3(K), dim3(1024), 0, ctx->stream, N, ld_dev, bg_dev, tlp_dev, logq_dev, logq_R, beta,
-                           logw_dev, self_normalized, E_out_dev, reward_out_dev, ess_out_dev);
-    }
-    GMMVI_LAUNCH_CHECK(ctx);
-    return GMMVI_OK;
+    return elr_launch(ctx, K, N, ld_dev, bg_dev, tlp_dev, logq_dev, logq_R, beta, logw_dev, self_normalized, E_out_dev,
+                      reward_out_dev, ess_out_dev);
+}
+
+int gmmvi_expected_log_ratios_parts(gmmvi_ctx* ctx, int K, int N, const float* ld_dev, const float* bg_dev,
+                                    const float* tlp_dev, const float* logq_parts_dev, int R, float beta,
+                                    const float* logw_dev, int self_normalized, float* E_out_dev, float* reward_out_dev,
+                                    float* ess_out_dev) {
+    GMMVI_ARG_CHECK(ctx, K >= 1 && N >= 1 && R >= 2);
+    GMMVI_ARG_CHECK(ctx, ld_dev && bg_dev && tlp_dev && logq_parts_dev && logw_dev);
+    int rc = gmmvi_flush_pending_combine(ctx);
+    if (rc != GMMVI_OK) return rc;
+    return elr_launch(ctx, K, N, ld_dev, bg_dev, tlp_dev, logq_parts_dev, R, beta, logw_dev, self_normalized, E_out_dev,
+                      reward_out_dev, ess_out_dev);
 }
 
 }  // extern "C"

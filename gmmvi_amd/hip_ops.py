@@ -506,18 +506,30 @@ def mmd_pair_sum(ctx, a, b, inv_bandwidth):
     return float(out.numpy().view(np.float64)[0])
 
 
-def expected_log_ratios(ctx, ld, bg, tlp, logq, beta, logw, self_normalized=True, reward_out=None, want_ess=False):
+def expected_log_ratios(ctx, ld, bg, tlp, logq, beta, logw, self_normalized=True, reward_out=None, want_ess=False,
+                        logq_parts=None):
+    """logq_parts ([R, N], R >= 2) replaces logq (pass None): the chunk partials of a component-split sweep, merged by the kernel
+    while it reads them."""
     k, n = ld.shape
-    _req(ld, (k, n), name="ld"); _req(bg, (n,), name="bg"); _req(tlp, (n,), name="tlp"); _req(logq, (n,), name="logq")
+    _req(ld, (k, n), name="ld"); _req(bg, (n,), name="bg"); _req(tlp, (n,), name="tlp")
     _req(logw, (k,), name="logw")
     if reward_out is not None:
         _req(reward_out, (k,), name="reward_out")
     e = ctx.empty((k,))
     ess = ctx.empty((k,)) if want_ess else None
-    ctx.check(ctx.lib.gmmvi_expected_log_ratios(ctx.handle, k, n, ld.ptr, bg.ptr, tlp.ptr, logq.ptr, float(beta),
-                                                logw.ptr, 1 if self_normalized else 0, e.ptr,
-                                                None if reward_out is None else reward_out.ptr,
-                                                None if ess is None else ess.ptr))
+    tail = (float(beta), logw.ptr, 1 if self_normalized else 0, e.ptr, None if reward_out is None else reward_out.ptr,
+            None if ess is None else ess.ptr)
+    if logq_parts is not None:
+        if logq is not None:
+            raise ValueError("expected_log_ratios: give logq or logq_parts, not both")
+        r = logq_parts.shape[0]
+        if r < 2:
+            raise ValueError("expected_log_ratios: logq_parts needs at least two partial rows")
+        _req(logq_parts, (r, n), name="logq_parts")
+        ctx.check(ctx.lib.gmmvi_expected_log_ratios_parts(ctx.handle, k, n, ld.ptr, bg.ptr, tlp.ptr, logq_parts.ptr, r, *tail))
+    else:
+        _req(logq, (n,), name="logq")
+        ctx.check(ctx.lib.gmmvi_expected_log_ratios(ctx.handle, k, n, ld.ptr, bg.ptr, tlp.ptr, logq.ptr, *tail))
     return e, ess
 
 

@@ -347,6 +347,12 @@ int gmmvi_update_components_iblr(gmmvi_ctx* ctx, int K, int D, float* means_dev,
 int gmmvi_expected_log_ratios(gmmvi_ctx* ctx, int K, int N, const float* ld_dev, const float* bg_dev,
                               const float* tlp_dev, const float* logq_dev, float beta, const float* logw_dev,
                               int self_normalized, float* E_out_dev, float* reward_out_dev, float* ess_out_dev);
+/* The same launch reading the log values of a component-split sweep as its R >= 2 chunk partials logq_parts_dev [R][N]
+ * (logq[n] = log sum_r exp(parts[r][n]), merged while read): the form the single-call iteration uses after a deferred merge. */
+int gmmvi_expected_log_ratios_parts(gmmvi_ctx* ctx, int K, int N, const float* ld_dev, const float* bg_dev,
+                                    const float* tlp_dev, const float* logq_parts_dev, int R, float beta,
+                                    const float* logw_dev, int self_normalized, float* E_out_dev, float* reward_out_dev,
+                                    float* ess_out_dev);
 /* TrustRegionBasedWeightUpdater (weight_updater.py:164-279) followed by GMM.replace_weights (models/gmm.py:173-181).
  * stepsize_dev[1] is the KL bound.  kl_eta_out_dev[2] (may be NULL) = (kl, eta). No-op when K == 1 (:275). */
 int gmmvi_update_weights_kl(gmmvi_ctx* ctx, int K, float* logw_dev, const float* E_dev, const float* stepsize_dev,

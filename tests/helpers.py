@@ -6,10 +6,10 @@ from oracle import targets as otargets, train as otrain
 
 def samtron_config(desired_samples, reuse_ratio=0.0, initial_stepsize=0.1, adaptive=None, updater="trust-region",
                    weight_updater="trust-region", snis=True, own=False, wstep=1.0, estimator="Stein", diag=False,
-                   selector="component-based", max_database_size=10000000):
+                   selector="component-based", max_database_size=10000000, temperature=1.0):
     """SAMTRON-style config dict with the keys of the reference's example_config.yml."""
     cfg = {
-        "temperature": 1.0, "use_sample_database": True, "max_database_size": max_database_size, "seed": 0,
+        "temperature": float(temperature), "use_sample_database": True, "max_database_size": max_database_size, "seed": 0,
         "model_initialization": {"use_diagonal_covs": bool(diag), "prior_mean": 0., "initial_cov": 1.0},
         "ng_estimator_type": estimator,
         "ng_estimator_config": dict({"only_use_own_samples": own, "use_self_normalized_importance_weights": snis},
