@@ -53,6 +53,17 @@ _sz = C.c_size_t
 _u64 = C.c_uint64
 _u32 = C.c_uint32
 
+MLP_MAX_LAYERS = 4             # gmmvi_mlp_desc: dense layers of the generic BNN (csrc/bnn_mlp.hip)
+MLP_ACTIVATIONS = {"linear": 0, "sigmoid": 1, "relu": 2, "tanh": 3}
+MLP_LOSSES = {"mse": 0, "sparse_categorical_crossentropy": 1}
+
+
+class MlpDesc(C.Structure):
+    """gmmvi_mlp_desc (include/gmmvi_hip.h)."""
+    _fields_ = [("n_layers", C.c_int32), ("widths", C.c_int32 * (MLP_MAX_LAYERS + 1)),
+                ("activations", C.c_int32 * MLP_MAX_LAYERS), ("loss", C.c_int32)]
+
+
 _PROTOS = {
     "gmmvi_device_count": (_i, []),
     "gmmvi_ctx_create": (_i, [C.POINTER(_p), _i]),
@@ -102,6 +113,8 @@ _PROTOS = {
     "gmmvi_bnn_predict": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p]),
     "gmmvi_target_bnn_classifier": (_i, [_p, _i, _i, _i, _i, _p, _p, _u64, _u32, _i, _f, _f, _p, _i, _p, _p]),
     "gmmvi_bnn_classifier_predict": (_i, [_p, _i, _i, _i, _p, _i, _p, _i, _p]),
+    "gmmvi_target_mlp": (_i, [_p, C.POINTER(MlpDesc), _i, _p, _p, _u64, _u32, _i, _f, _f, _p, _i, _p, _p]),
+    "gmmvi_mlp_predict": (_i, [_p, C.POINTER(MlpDesc), _p, _i, _p, _i, _p]),
     "gmmvi_target_talos": (_i, [_p, _p, _p, _p, _i, _p, _p]),
     "gmmvi_talos_fk": (_i, [_p, _p, _p, _i, _p, _p]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),

@@ -16,6 +16,11 @@ balanced 4-round Feistel network on 2h bits (h = ceil(ceil(log2 T) / 2)) with cy
 (L, R) -> (R, L xor (F_i(R) & (2^h - 1))), F_i(R) = word 0 of Philox4x32-10 with key (seed lo, seed hi) and counter
 (R | i << 24, e, c, 3).  Every epoch visits every row once.  ``minibatch_rows`` restates it in NumPy.
 
+Three classes evaluate the posterior: ``BNNRegression`` (two sigmoid hidden layers, csrc/bnn.hip: WINE),
+``BNNClassification`` (one ReLU hidden layer, csrc/bnn_classifier.hip: MNIST) and the generic ``BNN_LNPDF`` (one to three
+hidden layers, any of linear / sigmoid / ReLU / tanh per layer, MSE or sparse cross-entropy, csrc/bnn_mlp.hip), which
+stands where upstream's base class of the same name does.  All three share the minibatch stream below.
+
 The datasets do not ship with the package: ``dataset_dir`` (``environment_config["dataset_dir"]``), else the
 ``GMMVI_DATASET_DIR`` environment variable, names a directory laid out like upstream's ``datasets/`` folder:
 ``wine/wine_seed_{0..9}.npz``.
@@ -87,9 +92,11 @@ def minibatch_rows(seed, call, n, batch_size, num_data):
     return permute_rows(seed, call, p // num_data, p % num_data, num_data).reshape(int(n), int(batch_size))
 
 
-def num_parameters(num_features, hidden_units):
+def num_parameters(num_features, hidden_units, num_outputs=1):
+    """Per layer W [in, out], then b [out]; ``num_outputs`` is the width of the last layer (1 for a regressor, the number
+    of classes for a classifier)."""
     d, last = 0, int(num_features)
-    for width in list(hidden_units) + [1]:
+    for width in list(hidden_units) + [num_outputs]:
         d += last * int(width) + int(width)
         last = int(width)
     return d
@@ -382,3 +389,133 @@ class BNN_MNIST(BNNClassification):
 def make_MNIST_target(likelihood_scaling, prior_std, batch_size, dataset_dir=None, seed=0):
     return BNN_MNIST(likelihood_scaling=likelihood_scaling, prior_std=prior_std, batch_size=batch_size,
                      dataset_dir=dataset_dir, seed=seed)
+
+
+# ---- the generic network: any depth, activation and loss (BNN_LNPDF) -----------------------------------------------------
+MLP_LOSSES = ("mse", "sparse_categorical_crossentropy")
+
+
+class BNN_LNPDF(LNPDF):
+    """bnn.py:59-311: the posterior of a dense network features -> hidden_units ... -> outputs on minibatches of
+    ``batch_size`` rows under a zero-mean normal prior of standard deviation ``prior_std``:
+        log p(w) = s (-T mean_m loss_m - 0.5 sum_d w_d^2 / sd^2)
+    evaluated with its analytic gradient by csrc/bnn_mlp.hip.  In place of upstream's Keras objects:
+
+    ``hidden_units``: 1 to 3 hidden widths, each at most 128; at most 1024 features.
+    ``activations``: one name per layer, the output layer included, among "linear", "sigmoid", "relu", "tanh"; the output
+    layer's must be "linear".
+    ``loss``: "mse" (one output, float labels) or "sparse_categorical_crossentropy" (logits over ``num_classes`` classes,
+    2 to 16, integer labels in [0, num_classes)).
+    ``features`` [T, F], ``labels`` [T]: the training set; ``eval_sets`` maps "test" / "vali" to (features, labels) pairs
+    for ``expensive_metrics``.  A subclass may leave ``features`` out and override ``prepare_data`` instead, as upstream's
+    subclasses do; it returns (features, labels, eval_sets).
+    ``seed`` keys the minibatch stream (BNNRegression's: stream id 3); ``call_count`` is the number of evaluations so far.
+    ``dataset_seed`` is kept for ``prepare_data``."""
+
+    def __init__(self, likelihood_scaling=1., prior_std=1., batch_size=128, hidden_units=(8, 8), loss="mse",
+                 activations=("sigmoid", "sigmoid", "linear"), features=None, labels=None, num_classes=None,
+                 dataset_seed=-1, seed=0, eval_sets=None):
+        super().__init__(use_log_density_and_grad=True)
+        self.dataset_seed = int(dataset_seed)
+        if features is None:
+            features, labels, eval_sets = self.prepare_data()
+        if loss not in MLP_LOSSES:
+            raise ValueError(f"loss must be one of {MLP_LOSSES}, got {loss!r}")
+        if loss != "mse" and num_classes is None:
+            raise ValueError("num_classes is required for the sparse_categorical_crossentropy loss")
+        X = np.asarray(features, np.float32)
+        y = np.asarray(labels)
+        if X.ndim != 2 or y.shape != (X.shape[0],):
+            raise ValueError(f"features must be [T, F] and labels [T], got {X.shape} and {y.shape}")
+        self.loss = loss
+        self.num_outputs = 1 if loss == "mse" else int(num_classes)
+        self.hidden_units = tuple(int(h) for h in hidden_units)
+        self.activations = tuple(activations)
+        hip_ops.mlp_desc(X.shape[1], self.hidden_units, self.activations, loss, self.num_outputs)    # raises on a limit
+        if not 1 <= int(batch_size) <= min(X.shape[0], hip_ops.MLP_MAX_BATCH):
+            raise ValueError(f"batch_size must lie in [1, {min(X.shape[0], hip_ops.MLP_MAX_BATCH)}] (the training-set "
+                             f"size, at most {hip_ops.MLP_MAX_BATCH}), got {batch_size}")
+        if not prior_std > 0:
+            raise ValueError("prior_std must be positive")
+        if loss != "mse" and y.size and (not np.all(y == np.floor(y)) or y.min() < 0 or y.max() >= self.num_outputs):
+            raise ValueError(f"labels must be integers in [0, {self.num_outputs}) (num_classes), got values in "
+                             f"[{y.min()}, {y.max()}]")
+        self._label_dtype = np.float32 if loss == "mse" else np.int32
+        self.features, self.labels = X, y.astype(self._label_dtype)
+        self.num_classes = None if loss == "mse" else self.num_outputs
+        self.likelihood_scaling, self.prior_std = float(likelihood_scaling), float(prior_std)
+        self.batch_size, self.seed = int(batch_size), int(seed)
+        self.eval_sets = {k: (np.asarray(f, np.float32), np.asarray(l).astype(self._label_dtype))
+                          for k, (f, l) in (eval_sets or {}).items()}
+        self._call = 0
+        self.ctx = get_context()
+        self._X_dev, self._y_dev = self.ctx.asarray(X), self.ctx.asarray(self.labels, self._label_dtype)
+
+    def prepare_data(self):
+        """-> (features [T, F], labels [T], eval_sets or None); called when the constructor gets no ``features``."""
+        raise NotImplementedError
+
+    @property
+    def call_count(self):
+        return self._call
+
+    @property
+    def train_size(self):
+        return int(self.features.shape[0])
+
+    def get_num_dimensions(self):
+        return num_parameters(self.features.shape[1], self.hidden_units, self.num_outputs)
+
+    def _evaluate(self, x, want_grad):
+        x = self.ctx.asarray(x)
+        lp, grad = hip_ops.target_mlp(self.ctx, self._X_dev, self._y_dev, self.hidden_units, self.activations, self.loss,
+                                      self.num_outputs, self.seed, self._call, self.batch_size, self.likelihood_scaling,
+                                      self.prior_std, x, want_grad=want_grad)
+        if x.shape[0] >= 1:
+            self._call += 1
+        return lp, grad
+
+    def log_density(self, x):
+        return self._evaluate(x, False)[0]
+
+    def log_density_and_grad(self, x):
+        return self._evaluate(x, True)
+
+    def predict(self, samples, features):
+        """Network outputs [S, M] ("mse") or logits [S, M, C] of the weight vectors ``samples`` [S, D] on the rows
+        ``features`` [M, F]."""
+        return hip_ops.mlp_predict(self.ctx, self.hidden_units, self.activations, self.loss, self.num_outputs,
+                                   self.ctx.asarray(samples), self.ctx.asarray(np.asarray(features, np.float32)))
+
+    def bayesian_inference_loss(self, samples, dataset):
+        """bnn.py:290-310: the outputs averaged over the samples, then the loss and the second metric of every batch of
+        ``batch_size`` rows (stored order, the last batch partial), averaged over the batches in fp64 -> (loss, metric):
+        the MSE and the RMSE, or the cross-entropy from logits and the sparse categorical accuracy."""
+        features, labels = self.eval_sets[dataset]
+        out = self.predict(samples, features)
+        mean_out = (out.numpy() if hasattr(out, "numpy") else np.asarray(out)).astype(np.float64).mean(0)
+        losses, metrics = [], []
+        for b0 in range(0, len(labels), self.batch_size):
+            o, y = mean_out[b0:b0 + self.batch_size], labels[b0:b0 + self.batch_size]
+            if self.loss == "mse":
+                r = y.astype(np.float64) - o
+                losses.append(np.mean(r * r))
+                metrics.append(np.sqrt(losses[-1]))
+            else:
+                mx = o.max(1)
+                lse = mx + np.log(np.exp(o - mx[:, None]).sum(1))
+                losses.append(np.mean(lse - o[np.arange(len(y)), y]))
+                metrics.append(np.mean(o.argmax(1) == y))
+        return float(np.mean(losses)), float(np.mean(metrics))
+
+    def expensive_metrics(self, model, samples) -> dict:
+        """Keys as upstream's subclasses name them; for the "mse" loss the ``accuracy`` entries hold the RMSE, as
+        ``bi_test_accuracy`` does upstream (bnn.py:417-444)."""
+        metrics = dict()
+        if "test" in self.eval_sets:
+            loss, second = self.bayesian_inference_loss(samples, "test")
+            metrics.update({"bi_test_loss": loss, "bi_test_accuracy": second})
+        if "vali" in self.eval_sets:
+            loss, second = self.bayesian_inference_loss(samples, "vali")
+            metrics.update({"bi_vali_loss": loss, "bi_vali_accuracy": second})
+        return metrics

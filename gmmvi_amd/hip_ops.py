@@ -195,7 +195,101 @@ def bnn_classifier_predict(ctx, hidden, num_classes, W, X):
     return out
 
 
-TALOS_DIM = 34                                          # csrc/talos.hip: 28 joints, base position, roll / pitch / yaw
+MLP_MAX_FEATURES, MLP_MAX_HIDDEN, MLP_MAX_HIDDEN_LAYERS = 1024, 128, _lib.MLP_MAX_LAYERS - 1     # csrc/bnn_mlp.hip
+MLP_MIN_CLASSES, MLP_MAX_CLASSES, MLP_MAX_BATCH = 2, 16, 1024
+
+
+def mlp_num_parameters(num_features, hidden_units, num_outputs=1):
+    """Per layer W [in, out], then b [out], over num_features -> hidden_units ... -> num_outputs."""
+    d, last = 0, int(num_features)
+    for width in [int(h) for h in hidden_units] + [int(num_outputs)]:
+        d += last * width + width
+        last = width
+    return d
+
+
+def mlp_desc(num_features, hidden_units, activations, loss, num_outputs=1):
+    """The gmmvi_mlp_desc of a network, checked against what csrc/bnn_mlp.hip takes (ValueError names the limit).
+    activations: one name per layer, the output layer included ("linear" there); loss: "mse" (one output) or
+    "sparse_categorical_crossentropy" (num_outputs classes)."""
+    hidden = [int(h) for h in hidden_units]
+    acts = list(activations)
+    f, c = int(num_features), int(num_outputs)
+    if not 1 <= len(hidden) <= MLP_MAX_HIDDEN_LAYERS:
+        raise ValueError(f"hidden_units must name 1 to {MLP_MAX_HIDDEN_LAYERS} hidden layers, got {tuple(hidden)}")
+    if not 1 <= f <= MLP_MAX_FEATURES:
+        raise ValueError(f"the network takes 1 to {MLP_MAX_FEATURES} features, got {f}")
+    if not all(1 <= h <= MLP_MAX_HIDDEN for h in hidden):
+        raise ValueError(f"hidden layers must have 1 to {MLP_MAX_HIDDEN} units, got {tuple(hidden)}")
+    if len(acts) != len(hidden) + 1:
+        raise ValueError(f"activations must name one activation per layer, the output layer included "
+                         f"({len(hidden) + 1}), got {len(acts)}")
+    unknown = [a for a in acts if a not in _lib.MLP_ACTIVATIONS]
+    if unknown:
+        raise ValueError(f"activations must be among {sorted(_lib.MLP_ACTIVATIONS)}, got {unknown}")
+    if acts[-1] != "linear":
+        raise ValueError(f"the output layer's activation must be 'linear', got {acts[-1]!r}")
+    if loss not in _lib.MLP_LOSSES:
+        raise ValueError(f"loss must be one of {sorted(_lib.MLP_LOSSES)}, got {loss!r}")
+    if loss == "mse" and c != 1:
+        raise ValueError(f"the mse loss takes one output, got {c}")
+    if loss != "mse" and not MLP_MIN_CLASSES <= c <= MLP_MAX_CLASSES:
+        raise ValueError(f"num_classes must lie in [{MLP_MIN_CLASSES}, {MLP_MAX_CLASSES}], got {c}")
+    d = mlp_num_parameters(f, hidden, c)
+    if d > _lib.MAX_DIM_DIAG:
+        raise ValueError(f"the network has {d} parameters, more than the {_lib.MAX_DIM_DIAG} a diagonal mixture takes")
+    desc = _lib.MlpDesc()
+    desc.n_layers = len(hidden) + 1
+    for i, w in enumerate([f] + hidden + [c]):
+        desc.widths[i] = w
+    for i, a in enumerate(acts):
+        desc.activations[i] = _lib.MLP_ACTIVATIONS[a]
+    desc.loss = _lib.MLP_LOSSES[loss]
+    return desc
+
+
+def target_mlp(ctx, X, y, hidden_units, activations, loss, num_outputs, seed, call, batch_size, likelihood_scaling, prior_std,
+               x, want_grad=True):
+    """Generic Bayesian-neural-network posterior (csrc/bnn_mlp.hip).  X: [T, F] training features; y: [T] f32 labels (loss
+    "mse", num_outputs 1) or int32 labels in [0, num_outputs) ("sparse_categorical_crossentropy"); the minibatch rows come
+    from the stream of (seed, call).  -> (lp [n], grad [n, D])."""
+    t, f = X.shape
+    desc = mlp_desc(f, hidden_units, activations, loss, num_outputs)
+    d = mlp_num_parameters(f, hidden_units, num_outputs)
+    n = x.shape[0]
+    _req(X, (t, f), name="X"); _req(y, (t,), F32 if loss == "mse" else I32, name="y"); _req(x, (n, d), name="x")
+    if not 1 <= int(batch_size) <= min(t, MLP_MAX_BATCH):
+        raise ValueError(f"batch_size must lie in [1, {min(t, MLP_MAX_BATCH)}] (the training-set size, at most "
+                         f"{MLP_MAX_BATCH}), got {batch_size}")
+    if not prior_std > 0:
+        raise ValueError("prior_std must be positive")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_mlp(ctx.handle, desc, t, X.ptr, y.ptr, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                           int(call) & 0xFFFFFFFF, int(batch_size), float(likelihood_scaling),
+                                           float(prior_std), x.ptr, n, lp.ptr, None if grad is None else grad.ptr))
+    return lp, grad
+
+
+def mlp_predict(ctx, hidden_units, activations, loss, num_outputs, W, X):
+    """Network outputs of every weight vector on every row (csrc/bnn_mlp.hip), forward only.  W: [S, D], X: [M, F]
+    -> [S, M] ("mse") or logits [S, M, C]."""
+    m, f = X.shape
+    desc = mlp_desc(f, hidden_units, activations, loss, num_outputs)
+    d = mlp_num_parameters(f, hidden_units, num_outputs)
+    s = W.shape[0]
+    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
+    out = ctx.empty((s, m) if loss == "mse" else (s, m, int(num_outputs)))
+    if m > 0:
+        for s0 in range(0, s, 65535):                   # the kernel's grid takes at most 65535 weight vectors per launch
+            s1 = min(s, s0 + 65535)
+            ctx.check(ctx.lib.gmmvi_mlp_predict(ctx.handle, desc, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m,
+                                                out.rows(s0, s1).ptr))
+    return out
+
+
+TALOS_DIM = 34                                         # csrc/talos.hip: 28 joints, base position, roll / pitch / yaw
 TALOS_TABLE_SIZE = 8 + 28 * 28 + 4 * 16                 # header, joint records, tip records (talos_ik.py)
 
 

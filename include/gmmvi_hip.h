@@ -246,6 +246,36 @@ int gmmvi_target_bnn_classifier(gmmvi_ctx* ctx, int F, int H, int C, int T, cons
 int gmmvi_bnn_classifier_predict(gmmvi_ctx* ctx, int F, int H, int C, const float* W_dev, int S, const float* X_dev, int M,
                                  float* logits_out_dev);
 
+/* Generic Bayesian-neural-network posterior (target_distributions/bnn.py, BNN_LNPDF: any hidden_units list, one activation
+ * per layer, MSE or sparse categorical cross-entropy from logits) and its analytic gradient (csrc/bnn_mlp.hip).
+ * The network has n_layers dense layers, widths[0] = F inputs, widths[1 .. n_layers - 1] hidden units and widths[n_layers]
+ * outputs; W_dev[N,D] in the reference's layout, per layer W [in, out] row-major, then b [out].  loss 0: MSE, one output,
+ * y_dev[T] f32; loss 1: cross-entropy from logits, C = widths[n_layers] classes, y_dev[T] int32 in [0, C).  Sample n sees
+ * the B rows of gmmvi_target_bnn's minibatch stream (stream id 3) for (seed, call):
+ *   lp[n]   = likelihood_scaling (-(T/B) sum_j loss_j - 0.5 sum_d w_nd^2 / prior_std^2)
+ *   grad[n] = d lp[n] / d w_n      (ReLU derivative 1 where the pre-activation is positive, else 0)
+ * grad_out_dev may be NULL (lp is bitwise the same); N == 0 launches nothing.  2 <= n_layers <= 4, 1 <= F <= 1024, every
+ * hidden width in 1 .. 128 (the same cap for every hidden layer), 2 <= C <= 16, the output layer linear,
+ * 1 <= B <= min(T, 1024), D <= GMMVI_MAX_DIM_DIAG, prior_std > 0; anything else: GMMVI_ERR_ARG, and gmmvi_last_error names
+ * the limit.  A label outside [0, C) selects no logit.  Bitwise reproducible for a given (seed, call): no atomics. */
+#define GMMVI_MLP_MAX_LAYERS 4
+enum { GMMVI_MLP_LINEAR = 0, GMMVI_MLP_SIGMOID = 1, GMMVI_MLP_RELU = 2, GMMVI_MLP_TANH = 3 };
+enum { GMMVI_MLP_LOSS_MSE = 0, GMMVI_MLP_LOSS_CROSS_ENTROPY = 1 };
+typedef struct gmmvi_mlp_desc {
+    int32_t n_layers;                               /* dense layers, 2 .. 4 (one to three hidden layers) */
+    int32_t widths[GMMVI_MLP_MAX_LAYERS + 1];       /* F, the hidden widths, the output width */
+    int32_t activations[GMMVI_MLP_MAX_LAYERS];      /* one per layer: GMMVI_MLP_LINEAR / SIGMOID / RELU / TANH */
+    int32_t loss;                                   /* GMMVI_MLP_LOSS_MSE / GMMVI_MLP_LOSS_CROSS_ENTROPY */
+} gmmvi_mlp_desc;
+int gmmvi_target_mlp(gmmvi_ctx* ctx, const gmmvi_mlp_desc* net, int T, const float* X_dev, const void* y_dev, uint64_t seed,
+                     uint32_t call, int B, float likelihood_scaling, float prior_std, const float* W_dev, int N,
+                     float* lp_out_dev, float* grad_out_dev);
+
+/* The same network's outputs, forward only: out[s, m] (MSE) or logits[s, m, c] (cross-entropy) of X[m] under W[s].
+ * W_dev[S,D], X_dev[M,F]; S <= 65535; S == 0 or M == 0 launches nothing. */
+int gmmvi_mlp_predict(gmmvi_ctx* ctx, const gmmvi_mlp_desc* net, const float* W_dev, int S, const float* X_dev, int M,
+                      float* out_dev);
+
 /* Talos humanoid inverse kinematics (target_distributions/talos_ik.py; DESIGN.md 6, "Talos (defined, not reproduced)") and
  * its analytic gradient.  model_dev: the packed f32 table of talos_ik.TalosModel (28 revolute joints, 4 tips, lumped
  * masses); context_dev[3]: the left gripper's goal.  X_dev[N,34] = [q (28), p_b (3), roll, pitch, yaw]:
