@@ -70,6 +70,7 @@ _PROTOS = {
     "gmmvi_ctx_destroy": (None, [_p]),
     "gmmvi_last_error": (C.c_char_p, [_p]),
     "gmmvi_sync": (_i, [_p]),
+    "gmmvi_num_cus": (_i, [_p]),
     "gmmvi_malloc": (_i, [_p, _sz, C.POINTER(_p)]),
     "gmmvi_free": (_i, [_p, _p]),
     "gmmvi_upload": (_i, [_p, _p, _p, _sz]),

@@ -75,6 +75,8 @@ int gmmvi_sync(gmmvi_ctx* ctx) {
     return GMMVI_OK;
 }
 
+int gmmvi_num_cus(gmmvi_ctx* ctx) { return ctx ? ctx->num_cus : 0; }
+
 int gmmvi_malloc(gmmvi_ctx* ctx, size_t nbytes, void** out_dev) {
     GMMVI_ARG_CHECK(ctx, out_dev != nullptr);
     *out_dev = nullptr;

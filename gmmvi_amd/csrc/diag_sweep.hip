@@ -302,7 +302,8 @@ __global__ __launch_bounds__(256) void diag_stein_kernel(int K, int D, const flo
         __syncthreads();
     }
 #pragma unroll
-    for (int c = 0; c < DST_CG; ++c) n_used[c] = red[c][0];
+    // (all samples unless only the own ones count: a sample with ld = -inf has weight 0 and still counts in the divisor)
+    for (int c = 0; c < DST_CG; ++c) n_used[c] = own ? red[c][0] : (float)N;
     // pass 2: weighted sums of this piece's dimensions
     float sw[DST_CG], sg[DST_CG][DST_CH], sh[DST_CG][DST_CH], mu[DST_CG][DST_CH];
 #pragma unroll

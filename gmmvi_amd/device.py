@@ -78,6 +78,11 @@ class Context:
     def sync(self):
         self.check(self.lib.gmmvi_sync(self.handle))
 
+    @property
+    def num_cus(self):
+        """Compute units of the device (the kernels size their grids by it)."""
+        return int(self.lib.gmmvi_num_cus(self.handle))
+
     # ---- arrays ------------------------------------------------------------------------------------------
     def empty(self, shape, dtype=np.float32):
         return DeviceArray._alloc(self, shape, dtype)

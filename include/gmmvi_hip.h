@@ -73,6 +73,7 @@ int gmmvi_ctx_create(gmmvi_ctx** out, int device);
 void gmmvi_ctx_destroy(gmmvi_ctx* ctx);
 const char* gmmvi_last_error(gmmvi_ctx* ctx);          /* ctx may be NULL: last error of a failed create */
 int gmmvi_sync(gmmvi_ctx* ctx);
+int gmmvi_num_cus(gmmvi_ctx* ctx);                      /* compute units of the context's device: the launch geometries depend on it */
 int gmmvi_malloc(gmmvi_ctx* ctx, size_t nbytes, void** out_dev);
 int gmmvi_free(gmmvi_ctx* ctx, void* dev);
 int gmmvi_upload(gmmvi_ctx* ctx, void* dst_dev, const void* src_host, size_t nbytes);
