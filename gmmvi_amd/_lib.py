@@ -13,6 +13,7 @@ SELF_NORMALIZED, OWN_SAMPLES_ONLY, EXPLICIT_ESTIMATE = 1, 2, 4
 MAX_DIM = 64
 MORE_REGISTER_MAX_DIM = 21     # gmmvi_more: register-resident ridge system up to here, the tiled route above (D <= 63)
 MORE_BLOCKED_MIN_DIM, MORE_BLOCKED_MAX_DIM = 64, 128   # gmmvi_more_blocked: MORE from the blocked component layout
+MORE_DIAG_MAX_DIM = 1024       # gmmvi_more_diag: MORE for diagonal-covariance mixtures (F = 2 D + 1 features)
 MAX_DIM_BLOCKED = 512          # dense [K, D, D] factors (blocked kernels) exist up to here
 MAX_DIM_DIAG = 131072          # diagonal-covariance mixtures: csrc/diag_sweep.hip, csrc/diag.hip
 BLOCKED_ABOVE_DEFAULT = 50     # csrc/blocked.h: D > 50 runs the blocked (MFMA) kernels
@@ -124,6 +125,7 @@ _PROTOS = {
     "gmmvi_stein": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p]),
     "gmmvi_more": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "gmmvi_more_blocked": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
+    "gmmvi_more_diag": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "gmmvi_update_components_kl": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
     "gmmvi_update_components_kl_reference": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p]),
     "gmmvi_update_components_direct": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p]),

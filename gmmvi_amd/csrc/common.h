@@ -152,6 +152,15 @@ int gmmvi_update_components_kl_from_slab(gmmvi_ctx* ctx, int K, int D, const Ste
                                          float* chols_dev, const float* stepsizes_dev, float temperature, float l2_init,
                                          float* last_eta_dev, float* l2_dev, float* num_received_updates_dev,
                                          int32_t* success_out_dev, float* packed_out_dev);
+// more_blocked.hip: the fp64 panel solver of the MORE ridge systems (mb_chol_* / mb_backsub kernels), shared with
+// more_diag.hip.  G[kg][LDG][LDG] holds the lower triangles, LDG a multiple of 128 with LDG >= F + 1, row F the right-hand
+// side; fail[kg] must be zeroed by the caller.  attrs: dynamic-LDS attributes of the four kernels (once per context);
+// ws_budget: the workspace budget of one component group (GMMVI_MORE_WS_GB, read per call)
+size_t gmmvi_more_ws_budget_bytes();
+int gmmvi_more_panel_attrs(gmmvi_ctx* ctx);
+int gmmvi_more_panel_cholesky(gmmvi_ctx* ctx, const char* prof_name, int F, int LDG, int kg, int k0, const float* l2_dev,
+                              double* G, int* fail);
+int gmmvi_more_panel_backsub(gmmvi_ctx* ctx, int F, int LDG, int kg, const double* G, const int* fail, double* beta);
 // weights.hip: trust-region (mode 0) / direct (mode 1) weight update; exp_out (optional) receives exp(new log weights)
 int gmmvi_update_weights_internal(gmmvi_ctx* ctx, int mode, int K, float* logw_dev, const float* E_dev,
                                   const float* stepsize_dev, float beta, float* kl_eta_out_dev, float* exp_out_dev);

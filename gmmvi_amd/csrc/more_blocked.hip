@@ -39,6 +39,8 @@
 //   mb_gram_kernel 162 VGPR, 0 AGPR, 104 KB LDS at D = 128 (one 512-thread workgroup per CU); mb_chol_update_kernel 96 VGPR,
 //   0 AGPR, 68 KB LDS (two workgroups per CU); mb_chol_diag / _panel / mb_backsub / mb_whiten 26 / 64 / 40 / 16 VGPR.
 // Measured deviations and times: DESIGN.md section 4.
+// The Cholesky and back-substitution launches are also reachable as gmmvi_more_panel_* (common.h): more_diag.hip solves its
+// F = 2 D + 1 systems with them.
 #include "common.h"
 #include "blocked.h"
 #include "more_lse.h"
@@ -455,6 +457,56 @@ size_t align256(size_t b) { return (b + 255) / 256 * 256; }
 
 }  // namespace
 
+// ---- the panel solver as internal entry points (common.h): gmmvi_more_blocked below and more_diag.hip launch the same kernels ----
+size_t gmmvi_more_ws_budget_bytes() { return more_ws_budget_bytes(); }
+
+int gmmvi_more_panel_attrs(gmmvi_ctx* ctx) {
+    if (ctx->func_attr_done & 64u) return GMMVI_OK;          // per device: remembered per context
+    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_diag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(((size_t)TB * A_LD + TB) * sizeof(double))));
+    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_panel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(((size_t)64 * A_LD + (size_t)TB * (TB + 1) / 2) * sizeof(double))));
+    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)((size_t)2 * TB * UP_LD * sizeof(double))));
+    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_backsub_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(((size_t)TB * 66 + 2 * 32 * 33) * sizeof(double))));
+    ctx->func_attr_done |= 64u;
+    return GMMVI_OK;
+}
+
+// In-place Cholesky of the kg ridge systems G[kg][LDG][LDG] (lower triangle, F features, right-hand side in row F; ridge
+// l2_dev[k0 + kk] on all rows but the bias F - 1): one launch triple per 128-column panel
+int gmmvi_more_panel_cholesky(gmmvi_ctx* ctx, const char* prof_name, int F, int LDG, int kg, int k0, const float* l2_dev,
+                              double* G, int* fail) {
+    const int nblk = LDG / TB;
+    const size_t diag_lds = ((size_t)TB * A_LD + TB) * sizeof(double);
+    const size_t panel_lds = ((size_t)64 * A_LD + (size_t)TB * (TB + 1) / 2) * sizeof(double);
+    const size_t update_lds = (size_t)2 * TB * UP_LD * sizeof(double);
+    GMMVI_PROF(ctx, prof_name);
+    for (int jp = 0; TB * jp < F; ++jp) {
+        const int jb = TB * jp;
+        const int nbc = F - jb < TB ? F - jb : TB;
+        hipLaunchKernelGGL(mb_chol_diag_kernel, dim3(kg), dim3(512), diag_lds, ctx->stream, F, LDG, jb, k0, l2_dev, G, fail);
+        const int rows = F - (jb + nbc) + 1;                     // rows jb + nbc .. F
+        hipLaunchKernelGGL(mb_chol_panel_kernel, dim3((rows + 63) / 64, kg), dim3(64), panel_lds, ctx->stream, F, LDG, jb, G,
+                           fail);
+        const int nt = nblk - (jp + 1);                          // tile rows behind a full panel
+        if (nbc == TB && nt > 0)
+            hipLaunchKernelGGL(mb_chol_update_kernel, dim3(nt * (nt + 1) / 2, kg), dim3(512), update_lds, ctx->stream, LDG, jp, G,
+                               fail);
+        GMMVI_LAUNCH_CHECK(ctx);
+    }
+    return GMMVI_OK;
+}
+
+// beta[kk][0 .. F) (stride LDG doubles) from the factorised systems; LDG <= 128 * 66
+int gmmvi_more_panel_backsub(gmmvi_ctx* ctx, int F, int LDG, int kg, const double* G, const int* fail, double* beta) {
+    const size_t back_lds = ((size_t)LDG + 2 * 32 * 33) * sizeof(double);
+    hipLaunchKernelGGL(mb_backsub_kernel, dim3(kg), dim3(1024), back_lds, ctx->stream, F, LDG, G, fail, beta);
+    GMMVI_LAUNCH_CHECK(ctx);
+    return GMMVI_OK;
+}
+
 extern "C" int gmmvi_more_blocked(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const float* chols_dev,
                                   const float* X_dev, int N, const float* ld_dev, const float* logq_dev, const float* bg_dev,
                                   const float* tlp_dev, const int32_t* mapping_dev, int map_offset, int flags,
@@ -503,23 +555,13 @@ extern "C" int gmmvi_more_blocked(gmmvi_ctx* ctx, int K, int D, const float* pac
 
     const size_t whiten_lds = (size_t)D * 65 * sizeof(float);
     const size_t gram_lds = ((size_t)256 * PHI_LD + (size_t)(D + 3) * 64 + 256) * sizeof(float);
-    const size_t diag_lds = ((size_t)TB * A_LD + TB) * sizeof(double);
-    const size_t panel_lds = ((size_t)64 * A_LD + (size_t)TB * (TB + 1) / 2) * sizeof(double);
-    const size_t update_lds = (size_t)2 * TB * UP_LD * sizeof(double);
-    const size_t back_lds = ((size_t)LDG + 2 * 32 * 33) * sizeof(double);
     if (!(ctx->func_attr_done & 8u)) {
         GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)(((size_t)256 * PHI_LD + (size_t)(128 + 3) * 64 + 256) * sizeof(float))));
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_diag_kernel,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)diag_lds));
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_panel_kernel,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)panel_lds));
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_update_kernel,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)update_lds));
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_backsub_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)(((size_t)TB * 66 + 2 * 32 * 33) * sizeof(double))));
         ctx->func_attr_done |= 8u;
     }
+    rc = gmmvi_more_panel_attrs(ctx);
+    if (rc != GMMVI_OK) return rc;
 
     if (flags & GMMVI_SELF_NORMALIZED) {
         GMMVI_PROF(ctx, "more_blocked_lse");
@@ -543,26 +585,12 @@ extern "C" int gmmvi_more_blocked(gmmvi_ctx* ctx, int K, int D, const float* pac
                                LDG, Zt, G);
             GMMVI_LAUNCH_CHECK(ctx);
         }
-        {
-            GMMVI_PROF(ctx, "more_blocked_cholesky");
-            for (int jp = 0; TB * jp < F; ++jp) {
-                const int jb = TB * jp;
-                const int nbc = F - jb < TB ? F - jb : TB;
-                hipLaunchKernelGGL(mb_chol_diag_kernel, dim3(kg), dim3(512), diag_lds, ctx->stream, F, LDG, jb, k0, l2_dev, G,
-                                   fail);
-                const int rows = F - (jb + nbc) + 1;                     // rows jb + nbc .. F
-                hipLaunchKernelGGL(mb_chol_panel_kernel, dim3((rows + 63) / 64, kg), dim3(64), panel_lds, ctx->stream, F, LDG,
-                                   jb, G, fail);
-                const int nt = nblk - (jp + 1);                          // tile rows behind a full panel
-                if (nbc == TB && nt > 0)
-                    hipLaunchKernelGGL(mb_chol_update_kernel, dim3(nt * (nt + 1) / 2, kg), dim3(512), update_lds, ctx->stream, LDG, jp,
-                                       G, fail);
-                GMMVI_LAUNCH_CHECK(ctx);
-            }
-        }
+        rc = gmmvi_more_panel_cholesky(ctx, "more_blocked_cholesky", F, LDG, kg, k0, l2_dev, G, fail);
+        if (rc != GMMVI_OK) return rc;
         {
             GMMVI_PROF(ctx, "more_blocked_solve");
-            hipLaunchKernelGGL(mb_backsub_kernel, dim3(kg), dim3(1024), back_lds, ctx->stream, F, LDG, G, fail, beta);
+            rc = gmmvi_more_panel_backsub(ctx, F, LDG, kg, G, fail, beta);
+            if (rc != GMMVI_OK) return rc;
             hipLaunchKernelGGL(mb_unwhiten_right_kernel, dim3(D, kg), dim3(128), 0, ctx->stream, D, LDG, k0, pstride, linv_ofs,
                                packed_dev, beta, fail, T);
             hipLaunchKernelGGL(mb_unwhiten_left_kernel, dim3(D, kg), dim3(128), 0, ctx->stream, D, LDG, k0, pstride, linv_ofs,

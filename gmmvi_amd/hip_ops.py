@@ -531,6 +531,30 @@ def diag_stein(ctx, packed, x, ld, qgrad, bg, tgrad, d, mapping=None, map_offset
     return h_neg, g_neg
 
 
+def more_diag(ctx, packed, x, ld, logq, bg, tlp, l2, d, mapping=None, map_offset=0, self_normalized=True,
+              own_samples_only=False):
+    """Gradient-free MORE estimate of a diagonal mixture (gmmvi_more_diag: regression on [z^2, z, 1]) -> (h_neg_diag [K,D],
+    g_neg [K,D]); NaN rows for a component whose ridge system is not positive definite."""
+    if not 1 <= d <= _lib.MORE_DIAG_MAX_DIM:
+        raise ValueError(f"MORE estimator (diagonal route): D = {d} is outside the supported range "
+                         f"1 <= D <= {_lib.MORE_DIAG_MAX_DIM}")
+    k = packed.shape[0]
+    n = x.shape[0]
+    _req(packed, (k, diag_packed_stride(d)), name="packed"); _req(x, (n, d), name="x")
+    _req(logq, (n,), name="logq"); _req(tlp, (n,), name="tlp"); _req(l2, (k,), name="l2")
+    if own_samples_only:
+        _req(mapping, (n,), I32, "mapping")
+    else:
+        _req(ld, (k, n), name="ld"); _req(bg, (n,), name="bg")
+    flags = (_lib.SELF_NORMALIZED if self_normalized else 0) | (_lib.OWN_SAMPLES_ONLY if own_samples_only else 0)
+    h_neg = ctx.empty((k, d))
+    g_neg = ctx.empty((k, d))
+    ctx.check(ctx.lib.gmmvi_more_diag(ctx.handle, k, d, packed.ptr, x.ptr, n, None if ld is None else ld.ptr, logq.ptr,
+                                      None if bg is None else bg.ptr, tlp.ptr, None if mapping is None else mapping.ptr,
+                                      int(map_offset), flags, l2.ptr, h_neg.ptr, g_neg.ptr))
+    return h_neg, g_neg
+
+
 def diag_embed(ctx, chols_diag):
     """[K,D] sigma -> dense lower-triangular factors [K,D,D] = diag(sigma) for the dense density / sampling kernels."""
     k, d = chols_diag.shape

@@ -79,6 +79,9 @@ class GMMVI:
         sample_db = SampleDB.build_from_config(config, model.num_dimensions)
         parts = {name: factory(config, model, sample_db=sample_db, target_distribution=target_distribution)
                  for name, factory in GMMVI._MODULES}
+        # an estimator that reads function values only lets the selector run a target without log_density_and_grad
+        parts["sample_selector"].estimator_uses_target_gradients = getattr(parts["ng_estimator"], "uses_target_gradients",
+                                                                           True)
         return GMMVI(model, sample_db, config['temperature'], **parts)
 
     def train_iter(self):

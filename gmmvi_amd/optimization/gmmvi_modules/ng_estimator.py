@@ -19,6 +19,9 @@ class NgEstimator:
         if config["ng_estimator_type"] == "Stein":
             return SteinNgEstimator(temperature=temperature, model=gmm_wrapper, **config['ng_estimator_config'])
         elif config["ng_estimator_type"] == "MORE":
+            if gmm_wrapper.diagonal_covs:                     # no upstream counterpart: DESIGN.md section 6
+                return DiagonalMoreNgEstimator(temperature=temperature, model=gmm_wrapper,
+                                               **config['ng_estimator_config'])
             return MoreNgEstimator(temperature=temperature, model=gmm_wrapper, **config['ng_estimator_config'])
         raise ValueError(f"config['ng_estimator_type'] is '{config['ng_estimator_type']}' which is an unknown type")
 
@@ -34,6 +37,8 @@ class NgEstimator:
 class SteinNgEstimator(NgEstimator):
     """ng_estimator.py:123-263: one fused density+gradient pass (K1-K3) and one MFMA contraction over the samples
     per component (K6-K8) instead of the reference's K-step loop with [N,D,D] temporaries."""
+
+    uses_target_gradients = True
 
     def __init__(self, temperature, model, only_use_own_samples: bool, use_self_normalized_importance_weights: bool):
         super().__init__(temperature, model, True, only_use_own_samples, use_self_normalized_importance_weights)
@@ -86,6 +91,8 @@ class MoreNgEstimator(NgEstimator):
     and one fp64 Cholesky solve per component (csrc/more.hip): register-resident up to D = 21, tiled above (D <= 63; components of a blocked-path dimension are re-packed for the call).  64 <= D <= 128: csrc/more_blocked.hip
     (whitening from the dense L^-1 of the blocked component blocks, Cholesky spread over the chip)."""
 
+    uses_target_gradients = True       # upstream's MORE asks the selector for gradients (:291) although it does not read them
+
     def __init__(self, temperature, model, only_use_own_samples: bool, initial_l2_regularizer: float,
                  use_self_normalized_importance_weights: bool):
         super().__init__(temperature, model, True, only_use_own_samples,                   # :291 (True, as upstream)
@@ -95,7 +102,8 @@ class MoreNgEstimator(NgEstimator):
             raise ValueError("model.l2_regularizers must equal initial_l2_regularizer")
         if model.diagonal_covs:
             raise ValueError("MoreNgEstimator needs a full-covariance model (the reference's QuadFunc whitening, "
-                             "least_squares.py:126-191, has no diagonal branch)")
+                             "least_squares.py:126-191, has no diagonal branch); DiagonalMoreNgEstimator serves "
+                             "diagonal models")
         from ... import _lib
         d = model.num_dimensions
         self._blocked_route = _lib.MORE_BLOCKED_MIN_DIM <= d <= _lib.MORE_BLOCKED_MAX_DIM and d > _lib.blocked_above()
@@ -125,3 +133,50 @@ class MoreNgEstimator(NgEstimator):
         return more(ctx, m.packed, m.chol_cov, x, ld, model_densities, bg, tlp, m.l2_regularizers, d,
                     mapping=map_dev, map_offset=map_offset, self_normalized=self._use_self_normalized_importance_weights,
                     own_samples_only=self._only_use_own_samples)
+
+
+class DiagonalMoreNgEstimator(NgEstimator):
+    """MORE for a diagonal-covariance model (no upstream counterpart; definition: DESIGN.md section 6): the regression of
+    MoreNgEstimator on the sufficient statistics of a diagonal Gaussian, [z^2, z, 1] with z = (x - mu) / sigma, F = 2 D + 1
+    features (csrc/more_diag.hip), 1 <= D <= 1024.  It needs function values of the target only: with it a target that
+    implements ``log_density`` alone can be run (SampleSelector.get_target_grads)."""
+
+    uses_target_gradients = False
+
+    def __init__(self, temperature, model, only_use_own_samples: bool, initial_l2_regularizer: float,
+                 use_self_normalized_importance_weights: bool):
+        super().__init__(temperature, model, True, only_use_own_samples,                   # :291 (True, as upstream)
+                         use_self_normalized_importance_weights)
+        l2 = model.l2_regularizers.numpy()
+        if not np.all(l2 == np.float32(initial_l2_regularizer)):                          # :293
+            raise ValueError("model.l2_regularizers must equal initial_l2_regularizer")
+        if not model.diagonal_covs:
+            raise ValueError("DiagonalMoreNgEstimator needs a diagonal-covariance model; MoreNgEstimator serves "
+                             "full-covariance models")
+        from ... import _lib
+        if model.num_dimensions > _lib.MORE_DIAG_MAX_DIM:
+            raise ValueError(f"DiagonalMoreNgEstimator: the HIP kernels support D <= {_lib.MORE_DIAG_MAX_DIM} "
+                             "(DESIGN.md section 7)")
+        self.last_model_densities = None
+
+    def get_expected_hessian_and_grad(self, samples, mapping, background_densities, target_lnpdfs,
+                                      target_lnpdfs_grads=None):
+        """-> (expected_hessian_neg [K,D] (diagonals), expected_gradient_neg [K,D]); the gradients are not used."""
+        m = self._model
+        ctx = m.ctx
+        x = ctx.asarray(samples)
+        bg = ctx.asarray(background_densities)
+        tlp = ctx.asarray(target_lnpdfs)
+        k, d = m.num_components, m.num_dimensions
+        model_densities, ld = m.log_densities_also_individual(x)                          # :344
+        self.last_model_densities = model_densities
+        map_dev, map_offset = None, 0
+        if self._only_use_own_samples:
+            map_dev = ctx.asarray(mapping, np.int32)
+            host = getattr(m, "_mapping_max_hint", None)
+            mx = int(host) if host is not None else int(np.asarray(map_dev.numpy()).max())
+            map_offset = k - 1 - mx                                                        # :342
+        return hip_ops.more_diag(ctx, m.packed, x, ld, model_densities, bg, tlp, m.l2_regularizers, d,
+                                 mapping=map_dev, map_offset=map_offset,
+                                 self_normalized=self._use_self_normalized_importance_weights,
+                                 own_samples_only=self._only_use_own_samples)

@@ -6,11 +6,19 @@ from ...device import DeviceArray
 from ...models.gmm import STREAM_COMPONENT_NORMALS
 
 
+def _overrides_log_density_and_grad(target):
+    from ...experiments.target_distributions.lnpdf import LNPDF
+    return getattr(type(target), "log_density_and_grad", None) is not LNPDF.log_density_and_grad
+
+
 class SampleSelector:
     def __init__(self, target_distribution, model, sample_db):
         self.target_distribution = target_distribution
         self.model = model
         self.sample_db = sample_db
+        # False: the natural-gradient estimator reads function values only (DiagonalMoreNgEstimator); GMMVI.build_from_config
+        # sets it from the estimator's uses_target_gradients
+        self.estimator_uses_target_gradients = True
 
     @staticmethod
     def build_from_config(config, gmm_wrapper, sample_db, target_distribution):
@@ -27,9 +35,14 @@ class SampleSelector:
 
     def get_target_grads(self, samples):
         """sample_selector.py:69-78 -> (gradient, target).  Built-in targets evaluate log-density and gradient in one
-        fused kernel; user targets must provide log_density_and_grad (there is no autodiff here)."""
-        target, gradient = self.target_distribution.log_density_and_grad(samples)
+        fused kernel; user targets must provide log_density_and_grad (there is no autodiff here) -- unless the estimator
+        reads no gradients and the target's class leaves LNPDF.log_density_and_grad alone: then log_density is evaluated and
+        the gradient block of the sample database is zeros."""
         ctx = self.model.ctx
+        if not self.estimator_uses_target_gradients and not _overrides_log_density_and_grad(self.target_distribution):
+            target = ctx.asarray(self.target_distribution.log_density(samples))
+            return ctx.zeros((samples.shape[0], self.model.num_dimensions)), target
+        target, gradient = self.target_distribution.log_density_and_grad(samples)
         return ctx.asarray(gradient), ctx.asarray(target)
 
     def select_samples(self):

@@ -57,6 +57,7 @@ enum gmmvi_stein_flags {
                                          * one workgroup's registers; above (D <= 63; components of a blocked-path dimension are re-packed for the call) a tiled Gram launch and a blocked fp64
                                          * Cholesky in global memory take over */
 #define GMMVI_MORE_BLOCKED_MAX_DIM 128 /* gmmvi_more_blocked: 64 <= D <= 128 from the blocked component layout */
+#define GMMVI_MORE_DIAG_MAX_DIM 1024   /* gmmvi_more_diag: diagonal-covariance mixtures, 1 <= D <= 1024 (F = 2 D + 1 features) */
 #define GMMVI_MAX_DIM 64       /* register-resident kernels exist for D <= 64; they are used for D <= 50 (environment
                                 * GMMVI_BLOCKED_ABOVE, 16..64, moves that threshold) */
 #define GMMVI_MAX_DIM_BLOCKED 512   /* above the threshold, D <= 512: blocked kernels (dense L^-1 blocks, fp32 MFMA contractions)
@@ -341,6 +342,20 @@ int gmmvi_more_blocked(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, co
                        int N, const float* ld_dev, const float* logq_dev, const float* bg_dev, const float* tlp_dev,
                        const int32_t* mapping_dev, int map_offset, int flags, const float* l2_dev, float* H_neg_out_dev,
                        float* g_neg_out_dev);
+
+/* MORE for DIAGONAL-covariance mixtures (csrc/more_diag.hip; upstream has no diagonal branch, the definition is DESIGN.md
+ * section 6): the regression of gmmvi_more on the sufficient statistics of a diagonal Gaussian, phi(z) = [z^2, z, 1] with
+ * z = (x - mu) / sigma, F = 2 D + 1 features, bias unregularised, fp64 Gram matrix and Cholesky.  Needs function values of
+ * the target only.  packed_dev: the diagonal component blocks of gmmvi_diag_pack (stride gmmvi_diag_packed_stride(D)); X, ld
+ * (gmmvi_diag_mixture_eval on the same X), logq, bg, tlp, mapping, map_offset, flags and l2 as for gmmvi_more.
+ * Outputs: h_neg_diag[K,D] (the diagonals, as gmmvi_diag_stein returns them) = -2 theta_quad / sigma^2 and
+ * g_neg[K,D] = -theta_lin / sigma; NaN for a component whose ridge system is not positive definite.
+ * 1 <= D <= GMMVI_MORE_DIAG_MAX_DIM (= 1024); the (F + 1)^2 fp64 Gram matrices (38 MB per component at D = 1024) live in the
+ * context's workspace, components grouped under GMMVI_MORE_WS_GB as in gmmvi_more_blocked with results that do not depend on
+ * the group size.  D outside 1 ... 1024 or a missing pointer: GMMVI_ERR_ARG before any launch. */
+int gmmvi_more_diag(gmmvi_ctx* ctx, int K, int D, const float* packed_diag_dev, const float* X_dev, int N, const float* ld_dev,
+                    const float* logq_dev, const float* bg_dev, const float* tlp_dev, const int32_t* mapping_dev,
+                    int map_offset, int flags, const float* l2_dev, float* h_neg_diag_out_dev, float* g_neg_out_dev);
 
 /* ---- component updates --------------------------------------------------------------------------------------- */
 /* KLConstrainedNgBasedComponentUpdater.apply_NG_update (gmmvi_modules/ng_based_component_updater.py:431-524,
