@@ -65,6 +65,65 @@ class MlpDesc(C.Structure):
                 ("activations", C.c_int32 * MLP_MAX_LAYERS), ("loss", C.c_int32)]
 
 
+_i32 = C.c_int32
+
+
+class TargetSpec(C.Structure):
+    """gmmvi_target_spec: what a built-in target's ``_fast_path_target()`` returns; only the members of ``kind`` are set.
+    The device arrays behind the pointers belong to the target object, which outlives every plan that copies its spec."""
+    _fields_ = [("kind", _i32), ("mix_family", _i32), ("mix_K", _i32), ("mix_nu", _f), ("mix_packed", _p), ("mix_logw", _p),
+                ("planar_prior_std", _p), ("planar_goals", _p), ("planar_goals_count", _i32), ("planar_likelihood_std", _f),
+                ("logreg_A", _p), ("logreg_M", _i32), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
+                ("talos_model", _p), ("talos_context", _p)]
+
+
+class StepsizeRule(C.Structure):
+    """gmmvi_stepsize_rule."""
+    _fields_ = [("mode", _i32), ("min", _f), ("max", _f), ("inc", _f), ("dec", _f)]
+
+
+def stepsize_rule(src, improvement_based=True):
+    """The rule of an adapter object or of its config dict: both name the four numbers alike."""
+    if not improvement_based:
+        return StepsizeRule(0)
+    get = src.__getitem__ if isinstance(src, dict) else lambda name: getattr(src, name)
+    return StepsizeRule(1, get("min_stepsize"), get("max_stepsize"), get("stepsize_inc_factor"), get("stepsize_dec_factor"))
+
+
+class SamtronPlan(C.Structure):
+    """gmmvi_samtron_plan."""
+    _fields_ = [
+        ("K", _i32), ("D", _i32), ("N", _i32), ("target", TargetSpec),
+        ("means", _p), ("chols", _p), ("logw", _p), ("packed", _p), ("packed_new", _p),
+        ("stepsizes", _p), ("last_eta", _p), ("l2", _p), ("num_updates", _p), ("success_out", _p),
+        ("offsets", _p), ("max_per_component", _i32), ("n_old", _i32), ("bg_K", _i32), ("bg_packed", _p), ("bg_logw", _p),
+        ("bg_old", _p), ("bg_logw_new", _p), ("bg_log_share_old", _f), ("bg_log_share_new", _f),
+        ("seed", _u64), ("first_index", _u64),
+        ("db_samples", _p), ("db_tlp", _p), ("db_tgrad", _p), ("db_mapping", _p), ("mapping_base", _i32),
+        ("db_means", _p), ("db_chols", _p), ("db_packed", _p),
+        ("reward_prev", _p), ("reward_last", _p), ("reward_next", _p), ("weight_slot", _p), ("wstate", _p),
+        ("temperature", _f), ("l2_init", _f), ("component_stepsize", StepsizeRule), ("weight_stepsize", StepsizeRule),
+        ("weight_update_mode", _i32), ("stein_flags", _i32), ("presample_next", _i32), ("presampled", _i32), ("phase", _i32),
+    ]
+
+
+class ShardedPlan(C.Structure):
+    """gmmvi_sharded_plan."""
+    _fields_ = [
+        ("n_ranks", _i32), ("rank", _i32), ("K", _i32), ("D", _i32), ("N", _i32), ("target", TargetSpec),
+        ("means", _p), ("chols", _p), ("packed", _p), ("packed_new", _p),
+        ("stepsizes", _p), ("last_eta", _p), ("l2", _p), ("num_updates", _p), ("success_out", _p),
+        ("logw_all", _p), ("bg_logw", _p), ("offsets", _p), ("max_per_component", _i32),
+        ("seed", _u64), ("first_index", _u64),
+        ("e1", _p), ("e2", _p), ("e3", _p),
+        ("x_all", _p), ("tlp_all", _p), ("tgrad_all", _p), ("E_all", _p), ("reward_all", _p),
+        ("has_pending", _i32), ("reward_col_pending", _p), ("reward_prev", _p), ("reward_last", _p), ("reward_last_all", _p),
+        ("wstate", _p), ("temperature", _f), ("l2_init", _f),
+        ("component_stepsize", StepsizeRule), ("weight_stepsize", StepsizeRule),
+        ("stein_flags", _i32), ("presample_next", _i32), ("presampled", _i32), ("scratch", _p),
+    ]
+
+
 _PROTOS = {
     "gmmvi_device_count": (_i, []),
     "gmmvi_ctx_create": (_i, [C.POINTER(_p), _i]),
@@ -136,9 +195,10 @@ _PROTOS = {
     "gmmvi_update_weights_direct": (_i, [_p, _i, _p, _p, _p, _f]),
     "gmmvi_component_stepsize_improvement": (_i, [_p, _i, _p, _p, _p, _f, _f, _f, _f]),
     "gmmvi_weight_stepsize_improvement": (_i, [_p, _i, _p, _p, _p, _f, _f, _f, _f]),
-    "gmmvi_train_iter_samtron": (_i, [_p, _p]),
+    "gmmvi_struct_bytes": (_sz, [_i]),
+    "gmmvi_train_iter_samtron": (_i, [_p, C.POINTER(SamtronPlan)]),
     "gmmvi_sharded_scratch_floats": (_sz, [_i, _i, _i]),
-    "gmmvi_train_iter_sharded_phase": (_i, [_p, _p, _i]),
+    "gmmvi_train_iter_sharded_phase": (_i, [_p, C.POINTER(ShardedPlan), _i]),
     "gmmvi_comm_unique_id": (_i, [C.c_char_p]),
     "gmmvi_comm_init": (_i, [_p, C.c_char_p, _i, _i]),
     "gmmvi_comm_destroy": (_i, [_p]),

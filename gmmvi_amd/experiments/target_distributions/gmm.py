@@ -36,8 +36,8 @@ class GMM_LNPDF(LNPDF):
 
     def _fast_path_target(self):
         """Descriptor for the single-call iteration (optimization/fused.py)."""
-        return {"kind": 0, "family": self._family, "nu": float(self._nu), "K": int(self.target_means.shape[0]),
-                "packed": self._packed.ptr, "logw": self._logw.ptr}
+        return _lib.TargetSpec(kind=0, mix_family=self._family, mix_nu=float(self._nu), mix_K=int(self.target_means.shape[0]),
+                               mix_packed=self._packed.ptr, mix_logw=self._logw.ptr)
 
     def log_density(self, x):
         _, lp, _ = hip_ops.mixture_eval(self.ctx, self._packed, self._logw, self.ctx.asarray(x),

@@ -24,7 +24,7 @@ import os
 
 import numpy as np
 
-from ... import hip_ops
+from ... import _lib, hip_ops
 from ...device import get_context
 from .bnn import permute_rows
 from .lnpdf import LNPDF
@@ -131,8 +131,8 @@ class LogisticRegression(LNPDF):
 
     def _fast_path_target(self):
         """Descriptor for the single-call iteration (optimization/fused.py) and the phased sharded one (sharded.py)."""
-        return {"kind": 2, "A": self._A_dev.ptr, "M": self.num_data, "lr_prior_mean": self.prior_mean,
-                "lr_prior_std": self.prior_std}
+        return _lib.TargetSpec(kind=2, logreg_A=self._A_dev.ptr, logreg_M=self.num_data, logreg_prior_mean=self.prior_mean,
+                               logreg_prior_std=self.prior_std)
 
     def log_density(self, x):
         return hip_ops.target_logreg(self.ctx, self._A_dev, self.prior_mean, self.prior_std, self.ctx.asarray(x),

@@ -1,7 +1,7 @@
 """Planar n-link robot target (reference: src/gmmvi/experiments/target_distributions/planar_robot.py:11-138)."""
 import numpy as np
 
-from ... import hip_ops
+from ... import _lib, hip_ops
 from ...device import get_context
 from .lnpdf import LNPDF
 
@@ -31,8 +31,8 @@ class PlanarRobot(LNPDF):
 
     def _fast_path_target(self):
         """Descriptor for the single-call iteration (optimization/fused.py)."""
-        return {"kind": 1, "prior_std": self._prior_dev.ptr, "goals": self._goals_dev.ptr,
-                "G": int(self.goals.shape[0]), "lik_std": self.likelihood_std}
+        return _lib.TargetSpec(kind=1, planar_prior_std=self._prior_dev.ptr, planar_goals=self._goals_dev.ptr,
+                               planar_goals_count=int(self.goals.shape[0]), planar_likelihood_std=self.likelihood_std)
 
     def forward_kinematics(self, theta):
         """planar_robot.py:58-64 (host; metrics only)."""

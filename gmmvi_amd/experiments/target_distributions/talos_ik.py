@@ -21,7 +21,7 @@ import xml.etree.ElementTree as ET
 
 import numpy as np
 
-from ... import hip_ops
+from ... import _lib, hip_ops
 from ...device import get_context
 from .lnpdf import LNPDF
 
@@ -256,7 +256,7 @@ class Talos(LNPDF):
 
     def _fast_path_target(self):
         """Descriptor for the single-call iteration (optimization/fused.py) and the phased sharded one (sharded.py)."""
-        return {"kind": 4, "talos_model": self._table_dev.ptr, "talos_context": self._context_dev.ptr}
+        return _lib.TargetSpec(kind=4, talos_model=self._table_dev.ptr, talos_context=self._context_dev.ptr)
 
     def log_density(self, x):
         return hip_ops.target_talos(self.ctx, self._table_dev, self._context_dev, self.ctx.asarray(x), want_grad=False)[0]

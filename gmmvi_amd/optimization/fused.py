@@ -18,6 +18,7 @@ import os
 import numpy as np
 
 from .. import _lib, hip_ops
+from .._lib import SamtronPlan             # noqa: F401  (the plan's mirror lives with the other C structs)
 from .gmmvi_modules.sample_selector import VipsSampleSelector
 from .gmmvi_modules.ng_estimator import SteinNgEstimator
 from .gmmvi_modules.ng_based_component_updater import KLConstrainedNgBasedComponentUpdater
@@ -27,32 +28,6 @@ from .gmmvi_modules.weight_stepsize_adaptation import (FixedWeightStepsizeAdapta
                                                        ImprovementBasedWeightStepsizeAdaptation)
 from .gmmvi_modules.weight_updater import DirectWeightUpdater, TrustRegionBasedWeightUpdater
 from .gmmvi_modules.component_adaptation import FixedComponentAdaptation
-
-_f, _i, _p = C.c_float, C.c_int32, C.c_void_p
-
-
-class SamtronPlan(C.Structure):
-    """struct gmmvi_samtron_plan (include/gmmvi_hip.h)."""
-    _fields_ = [
-        ("K", _i), ("D", _i), ("N", _i), ("target_kind", _i), ("target_family", _i), ("target_K", _i),
-        ("target_nu", _f), ("target_packed", _p), ("target_logw", _p), ("planar_prior_std", _p), ("planar_goals", _p),
-        ("planar_goals_count", _i), ("planar_likelihood_std", _f),
-        ("means", _p), ("chols", _p), ("logw", _p), ("packed", _p), ("packed_new", _p),
-        ("stepsizes", _p), ("last_eta", _p), ("l2", _p), ("num_updates", _p), ("success_out", _p),
-        ("offsets", _p), ("max_per_component", _i), ("n_old", _i), ("bg_K", _i), ("bg_packed", _p), ("bg_logw", _p),
-        ("bg_old", _p), ("bg_logw_new", _p), ("bg_log_share_old", _f), ("bg_log_share_new", _f),
-        ("seed", C.c_uint64), ("first_index", C.c_uint64),
-        ("db_samples", _p), ("db_tlp", _p), ("db_tgrad", _p), ("db_mapping", _p), ("mapping_base", _i),
-        ("db_means", _p), ("db_chols", _p), ("db_packed", _p),
-        ("reward_prev", _p), ("reward_last", _p), ("reward_next", _p), ("weight_slot", _p), ("wstate", _p),
-        ("temperature", _f), ("l2_init", _f),
-        ("component_stepsize_mode", _i), ("cs_min", _f), ("cs_max", _f), ("cs_inc", _f), ("cs_dec", _f),
-        ("weight_stepsize_mode", _i), ("ws_min", _f), ("ws_max", _f), ("ws_inc", _f), ("ws_dec", _f),
-        ("weight_update_mode", _i), ("stein_flags", _i), ("presample_next", _i), ("presampled", _i), ("phase", _i),
-        ("logreg_A", _p), ("logreg_M", _i), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
-        ("talos_model", _p), ("talos_context", _p),
-    ]
-
 
 class SamtronFastPath:
     def __init__(self, gmmvi):
@@ -74,10 +49,7 @@ class SamtronFastPath:
         self._prefetch = None
         self._pinned = None              # (pinned host pointer, floats, NumPy view)
         self._event = None
-        lib = _lib.load()
-        lib.gmmvi_train_iter_samtron.restype = C.c_int
-        lib.gmmvi_train_iter_samtron.argtypes = [C.c_void_p, C.POINTER(SamtronPlan)]
-        self._fn = lib.gmmvi_train_iter_samtron
+        self._fn = _lib.load().gmmvi_train_iter_samtron
 
     # ---- eligibility -----------------------------------------------------------------------------------------------------
     def _check_static(self):
@@ -204,15 +176,7 @@ class SamtronFastPath:
         m = g.model
         model = m.model
         sel = g.sample_selector
-        tgt = sel.target_distribution._fast_path_target()
-        p.target_kind = tgt["kind"]
-        p.target_family, p.target_K, p.target_nu = tgt.get("family", 0), tgt.get("K", 0), tgt.get("nu", 0.0)
-        p.target_packed, p.target_logw = tgt.get("packed"), tgt.get("logw")
-        p.planar_prior_std, p.planar_goals = tgt.get("prior_std"), tgt.get("goals")
-        p.planar_goals_count, p.planar_likelihood_std = tgt.get("G", 0), tgt.get("lik_std", 0.0)
-        p.logreg_A, p.logreg_M = tgt.get("A"), tgt.get("M", 0)
-        p.logreg_prior_mean, p.logreg_prior_std = tgt.get("lr_prior_mean", 0.0), tgt.get("lr_prior_std", 0.0)
-        p.talos_model, p.talos_context = tgt.get("talos_model"), tgt.get("talos_context")
+        p.target = sel.target_distribution._fast_path_target()
         p.means, p.chols, p.logw = model.means.ptr, model.chol_cov.ptr, model.log_weights.ptr
         p.packed, p.packed_new = packed_cur.ptr, packed_new.ptr
         p.stepsizes, p.last_eta, p.l2 = m.stepsizes.ptr, m.last_log_etas.ptr, m.l2_regularizers.ptr
@@ -224,18 +188,8 @@ class SamtronFastPath:
         ws, cs, wu = g.weight_stepsize_adapter, g.component_stepsize_adapter, g.weight_updater
         p.wstate = ws._state.ptr
         p.temperature, p.l2_init = float(g.temperature), float(m.initial_regularizer)
-        if type(cs) is ImprovementBasedComponentStepsizeAdaptation:
-            p.component_stepsize_mode = 1
-            p.cs_min, p.cs_max = cs.min_stepsize, cs.max_stepsize
-            p.cs_inc, p.cs_dec = cs.stepsize_inc_factor, cs.stepsize_dec_factor
-        else:
-            p.component_stepsize_mode = 0
-        if type(ws) is ImprovementBasedWeightStepsizeAdaptation:
-            p.weight_stepsize_mode = 1
-            p.ws_min, p.ws_max = ws.min_stepsize, ws.max_stepsize
-            p.ws_inc, p.ws_dec = ws.stepsize_inc_factor, ws.stepsize_dec_factor
-        else:
-            p.weight_stepsize_mode = 0
+        p.component_stepsize = _lib.stepsize_rule(cs, type(cs) is ImprovementBasedComponentStepsizeAdaptation)
+        p.weight_stepsize = _lib.stepsize_rule(ws, type(ws) is ImprovementBasedWeightStepsizeAdaptation)
         p.weight_update_mode = 0 if type(wu) is TrustRegionBasedWeightUpdater else 1
         p.stein_flags = _lib.SELF_NORMALIZED if g.ng_estimator._use_self_normalized_importance_weights else 0
         if self.explicit_estimate:

@@ -29,35 +29,9 @@ import time
 
 import numpy as np
 
+from ._lib import ShardedPlan                # noqa: F401  (the plan's mirror lives with the other C structs)
+
 FLOAT32_MIN = float(np.finfo(np.float32).min)
-
-
-import ctypes as _C
-
-_f, _i, _p = _C.c_float, _C.c_int32, _C.c_void_p
-
-
-class ShardedPlan(_C.Structure):
-    """struct gmmvi_sharded_plan (include/gmmvi_hip.h)."""
-    _fields_ = [
-        ("n_ranks", _i), ("rank", _i), ("K", _i), ("D", _i), ("N", _i),
-        ("target_kind", _i), ("target_family", _i), ("target_K", _i), ("target_nu", _f),
-        ("target_packed", _p), ("target_logw", _p), ("planar_prior_std", _p), ("planar_goals", _p),
-        ("planar_goals_count", _i), ("planar_likelihood_std", _f),
-        ("means", _p), ("chols", _p), ("packed", _p), ("packed_new", _p),
-        ("stepsizes", _p), ("last_eta", _p), ("l2", _p), ("num_updates", _p), ("success_out", _p),
-        ("logw_all", _p), ("bg_logw", _p), ("offsets", _p), ("max_per_component", _i),
-        ("seed", _C.c_uint64), ("first_index", _C.c_uint64),
-        ("e1", _p), ("e2", _p), ("e3", _p),
-        ("x_all", _p), ("tlp_all", _p), ("tgrad_all", _p), ("E_all", _p), ("reward_all", _p),
-        ("has_pending", _i), ("reward_col_pending", _p), ("reward_prev", _p), ("reward_last", _p), ("reward_last_all", _p),
-        ("wstate", _p), ("temperature", _f), ("l2_init", _f),
-        ("component_stepsize_mode", _i), ("cs_min", _f), ("cs_max", _f), ("cs_inc", _f), ("cs_dec", _f),
-        ("weight_stepsize_mode", _i), ("ws_min", _f), ("ws_max", _f), ("ws_inc", _f), ("ws_dec", _f),
-        ("stein_flags", _i), ("presample_next", _i), ("presampled", _i), ("scratch", _p),
-        ("logreg_A", _p), ("logreg_M", _i), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
-        ("talos_model", _p), ("talos_context", _p),
-    ]
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -356,18 +330,10 @@ class ShardedGMMVI:
         f.success = ctx.empty((K,), np.int32)
         offsets = np.concatenate([[0], np.cumsum(self.counts_loc)]).astype(np.int32)
         f.offsets = ctx.asarray(offsets, np.int32)
-        t = tgt._fast_path_target()
-        f.target_keepalive = t
+        f.target_keepalive = tgt                       # its device arrays are what the plan's target points into
         p = ShardedPlan()
         p.n_ranks, p.rank, p.K, p.D, p.N = R, self.rank, K, D, N
-        p.target_kind = t["kind"]
-        p.target_family, p.target_K, p.target_nu = t.get("family", 0), t.get("K", 0), t.get("nu", 0.0)
-        p.target_packed, p.target_logw = t.get("packed"), t.get("logw")
-        p.planar_prior_std, p.planar_goals = t.get("prior_std"), t.get("goals")
-        p.planar_goals_count, p.planar_likelihood_std = t.get("G", 0), t.get("lik_std", 0.0)
-        p.logreg_A, p.logreg_M = t.get("A"), t.get("M", 0)
-        p.logreg_prior_mean, p.logreg_prior_std = t.get("lr_prior_mean", 0.0), t.get("lr_prior_std", 0.0)
-        p.talos_model, p.talos_context = t.get("talos_model"), t.get("talos_context")
+        p.target = tgt._fast_path_target()
         p.e1, p.e2, p.e3 = f.e1.ptr, f.e2.ptr, f.e3.ptr
         p.x_all, p.tlp_all, p.tgrad_all = f.x_all.ptr, f.tlp_all.ptr, f.tgrad_all.ptr
         p.E_all, p.reward_all = f.E_all.ptr, f.reward_all.ptr
@@ -375,12 +341,7 @@ class ShardedGMMVI:
         p.seed = int(self.seed) & 0xFFFFFFFFFFFFFFFF
         p.wstate = self.wstate.ptr
         p.temperature, p.l2_init = self.temperature, 1e-12
-        p.component_stepsize_mode = 1
-        p.cs_min, p.cs_max = self.cs["min_stepsize"], self.cs["max_stepsize"]
-        p.cs_inc, p.cs_dec = self.cs["stepsize_inc_factor"], self.cs["stepsize_dec_factor"]
-        p.weight_stepsize_mode = 1
-        p.ws_min, p.ws_max = self.ws["min_stepsize"], self.ws["max_stepsize"]
-        p.ws_inc, p.ws_dec = self.ws["stepsize_inc_factor"], self.ws["stepsize_dec_factor"]
+        p.component_stepsize, p.weight_stepsize = _lib.stepsize_rule(self.cs), _lib.stepsize_rule(self.ws)
         p.stein_flags = _lib.SELF_NORMALIZED if snis else 0
         p.scratch = f.scratch.ptr
         f.plan, f.presampled = p, False
@@ -409,7 +370,7 @@ class ShardedGMMVI:
         p.reward_last = ring + 4 * (Kt * last + self.lo)
         p.reward_prev = ring + 4 * (Kt * prev + self.lo)
         p.presampled, p.presample_next = int(f.presampled), int(f.presample)
-        call = lambda phase: ctx.check(ctx.lib.gmmvi_train_iter_sharded_phase(ctx.handle, _C.byref(p), phase))
+        call = lambda phase: ctx.check(ctx.lib.gmmvi_train_iter_sharded_phase(ctx.handle, p, phase))
         call(1)
         ex.allgather_inplace(f.e1, f.s1)
         call(2)

@@ -418,6 +418,38 @@ int gmmvi_weight_stepsize_improvement(gmmvi_ctx* ctx, int K, const float* logw_d
                                       float dec_factor);
 
 /* ---- single-call iteration ------------------------------------------------------------------------------------- */
+/* The built-in target of an iteration, described once for both plans below.  Only the members of `kind` are read. */
+typedef struct gmmvi_target_spec {
+    int32_t kind;                         /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot, 2: logistic regression,
+                                           * 4: Talos (gmmvi_target_talos); any other value, 3 included (no target has it):
+                                           * GMMVI_ERR_ARG */
+    /* kind 0 */
+    int32_t mix_family, mix_K;            /* enum gmmvi_family, number of target components */
+    float mix_nu;
+    const float* mix_packed;              /* [mix_K, stride] */
+    const float* mix_logw;                /* [mix_K] */
+    /* kind 1 (gmmvi_target_planar) */
+    const float* planar_prior_std;        /* [D] */
+    const float* planar_goals;            /* [planar_goals_count, 2] */
+    int32_t planar_goals_count;
+    float planar_likelihood_std;
+    /* kind 2 (gmmvi_target_logreg): the signed data matrix [logreg_M, D], the isotropic normal prior */
+    const float* logreg_A;
+    int32_t logreg_M;
+    float logreg_prior_mean, logreg_prior_std;
+    /* kind 4 (gmmvi_target_talos, D == 34): the packed model table, the left gripper's goal [3] */
+    const float* talos_model;
+    const float* talos_context;
+} gmmvi_target_spec;
+/* One stepsize rule (component_stepsize_adaptation.py:165-188, weight_stepsize_adaptation.py:141-156). */
+typedef struct gmmvi_stepsize_rule {
+    int32_t mode;                         /* 0 fixed, 1 improvement-based (the bounds and factors are read for 1 only) */
+    float min, max, inc, dec;
+} gmmvi_stepsize_rule;
+/* sizeof of the structs a binding has to mirror by hand: 0 gmmvi_target_spec, 1 gmmvi_stepsize_rule, 2 gmmvi_samtron_plan,
+ * 3 gmmvi_sharded_plan; anything else: 0.  Needs no device. */
+size_t gmmvi_struct_bytes(int which);
+
 /* GMMVI.train_iter() (optimization/gmmvi.py:146-174) for the SAMTRON design choices with a component-based sample
  * selector: Stein estimator, KL-constrained component update, trust-region or direct weight update, improvement-based or
  * fixed stepsizes, built-in target.  The call is exactly the composition of the entry points above in the order the plug-in
@@ -430,17 +462,7 @@ int gmmvi_weight_stepsize_improvement(gmmvi_ctx* ctx, int K, const float* logw_d
  * n_old == 0 and bg_packed == NULL the background components are the model's own (one sweep for both). */
 typedef struct gmmvi_samtron_plan {
     int32_t K, D, N;                      /* components, dimension, samples of this iteration (sum of the counts) */
-    int32_t target_kind;                  /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot, 2: logistic regression,
-                                           * 4: Talos (gmmvi_target_talos); any other value, 3 included (no target has it):
-                                           * GMMVI_ERR_ARG */
-    int32_t target_family, target_K;      /* enum gmmvi_family, number of target components */
-    float target_nu;
-    const float* target_packed;           /* [target_K, stride] */
-    const float* target_logw;             /* [target_K] */
-    const float* planar_prior_std;        /* [D] */
-    const float* planar_goals;            /* [G, 2] */
-    int32_t planar_goals_count;
-    float planar_likelihood_std;
+    gmmvi_target_spec target;             /* checked before the rest of the plan */
     /* model state (in/out) */
     float* means; float* chols; float* logw;          /* [K,D], [K,D,D], [K] */
     const float* packed;                  /* parameter blocks of the CURRENT components [K, stride] */
@@ -468,10 +490,7 @@ typedef struct gmmvi_samtron_plan {
     float* wstate;                        /* [2]: weight stepsize, previous ELBO proxy */
     /* hyper-parameters */
     float temperature, l2_init;
-    int32_t component_stepsize_mode;      /* 0 fixed, 1 improvement-based */
-    float cs_min, cs_max, cs_inc, cs_dec;
-    int32_t weight_stepsize_mode;         /* 0 fixed, 1 improvement-based */
-    float ws_min, ws_max, ws_inc, ws_dec;
+    gmmvi_stepsize_rule component_stepsize, weight_stepsize;   /* applied to `stepsizes` / `wstate` ahead of the updates */
     int32_t weight_update_mode;           /* 0 trust-region, 1 direct */
     int32_t stein_flags;                  /* enum gmmvi_stein_flags (own-samples-only is not supported here;
                                            * GMMVI_EXPLICIT_ESTIMATE: results bit-equal to the module-by-module calls) */
@@ -489,13 +508,6 @@ typedef struct gmmvi_samtron_plan {
      * updated components but not the weights: with sample reuse the effective sample sizes of the NEXT iteration's window
      * (sample_selector.py:140-202), read back asynchronously, so that the next iteration starts without waiting for them. */
     int32_t phase;
-    /* target_kind 2 (gmmvi_target_logreg): the signed data matrix [logreg_M, D], the isotropic normal prior */
-    const float* logreg_A;
-    int32_t logreg_M;
-    float logreg_prior_mean, logreg_prior_std;
-    /* target_kind 4 (gmmvi_target_talos): the packed model table, the left gripper's goal [3] */
-    const float* talos_model;
-    const float* talos_context;
 } gmmvi_samtron_plan;
 int gmmvi_train_iter_samtron(gmmvi_ctx* ctx, const gmmvi_samtron_plan* plan);
 
@@ -519,11 +531,7 @@ int gmmvi_train_iter_samtron(gmmvi_ctx* ctx, const gmmvi_samtron_plan* plan);
 typedef struct gmmvi_sharded_plan {
     int32_t n_ranks, rank;
     int32_t K, D, N;                      /* LOCAL components, dimension, samples of ALL ranks (N % n_ranks == 0) */
-    int32_t target_kind, target_family, target_K;
-    float target_nu;
-    const float* target_packed; const float* target_logw;
-    const float* planar_prior_std; const float* planar_goals;
-    int32_t planar_goals_count; float planar_likelihood_std;
+    gmmvi_target_spec target;             /* as in gmmvi_samtron_plan */
     /* local model state (in/out) */
     float* means; float* chols; const float* packed; float* packed_new;
     float* stepsizes; float* last_eta; float* l2; float* num_updates; int32_t* success_out;
@@ -545,8 +553,7 @@ typedef struct gmmvi_sharded_plan {
     const float* reward_last_all;         /* [K * n_ranks] the newest column (weight stepsize rule) */
     float* wstate;                        /* [2] weight stepsize, previous ELBO proxy */
     float temperature, l2_init;
-    int32_t component_stepsize_mode; float cs_min, cs_max, cs_inc, cs_dec;
-    int32_t weight_stepsize_mode; float ws_min, ws_max, ws_inc, ws_dec;
+    gmmvi_stepsize_rule component_stepsize, weight_stepsize;
     int32_t stein_flags;
     /* as in gmmvi_samtron_plan: phase 4 draws the NEXT iteration's local samples (Philox indices first_index + N ..) into this
      * rank's part of e1 as riders of the expected-log-ratio launch; phase 1 of a call with presampled != 0 skips its draw */
@@ -554,13 +561,6 @@ typedef struct gmmvi_sharded_plan {
     /* scratch that lives across the four phases (component log densities, merged mixture arrays): caller-owned so that
      * several plans can take turns on one context; at least gmmvi_sharded_scratch_floats(K, D, N) floats */
     float* scratch;
-    /* target_kind 2: as in gmmvi_samtron_plan */
-    const float* logreg_A;
-    int32_t logreg_M;
-    float logreg_prior_mean, logreg_prior_std;
-    /* target_kind 4: as in gmmvi_samtron_plan */
-    const float* talos_model;
-    const float* talos_context;
 } gmmvi_sharded_plan;
 size_t gmmvi_sharded_scratch_floats(int K, int D, int N);
 int gmmvi_train_iter_sharded_phase(gmmvi_ctx* ctx, const gmmvi_sharded_plan* plan, int phase /* 1..4 */);

@@ -75,6 +75,17 @@ def test_library_exports_every_declared_symbol(built_lib):
     assert built_lib.gmmvi_device_count() >= 0
 
 
+def test_struct_mirrors_have_the_sizes_of_the_c_structs(built_lib):
+    """The ctypes mirrors in _lib.py are kept by hand: a member missing, doubled or of another width shows in the size.  (Two
+    swapped members of equal width do not; the bit-equality tests of the two iterations on the GPU catch those.)"""
+    import ctypes
+    from gmmvi_amd import _lib
+    mirrors = (_lib.TargetSpec, _lib.StepsizeRule, _lib.SamtronPlan, _lib.ShardedPlan)
+    for which, mirror in enumerate(mirrors):
+        assert built_lib.gmmvi_struct_bytes(which) == ctypes.sizeof(mirror) > 0, mirror.__name__
+    assert built_lib.gmmvi_struct_bytes(-1) == 0 and built_lib.gmmvi_struct_bytes(len(mirrors)) == 0
+
+
 def test_context_creation_fails_loudly_without_gpu(built_lib):
     from gmmvi_amd import _lib
     if _lib.device_count() > 0:

@@ -263,12 +263,11 @@ def test_unknown_target_kind_is_an_argument_error():
     lib = _lib.load()
     for kind in (3, 7, -1):
         p = ShardedPlan()
-        p.target_kind = kind
+        p.target.kind = kind
         assert lib.gmmvi_train_iter_sharded_phase(ctx.handle, C.byref(p), 1) == -2
         assert "target_kind" in ctx.lib.gmmvi_last_error(ctx.handle).decode()
         q = SamtronPlan()
-        q.target_kind = kind
-        lib.gmmvi_train_iter_samtron.argtypes = [C.c_void_p, C.POINTER(SamtronPlan)]
+        q.target.kind = kind
         assert lib.gmmvi_train_iter_samtron(ctx.handle, C.byref(q)) == -2
         assert "target_kind" in ctx.lib.gmmvi_last_error(ctx.handle).decode()
     ctx.sync()

@@ -111,12 +111,11 @@ def test_target_kind_4_needs_its_model():
     ctx = get_context()
     lib = _lib.load()
     p = ShardedPlan()
-    p.target_kind = 4
+    p.target.kind = 4
     assert lib.gmmvi_train_iter_sharded_phase(ctx.handle, C.byref(p), 1) == -2
     assert "talos_model" in ctx.lib.gmmvi_last_error(ctx.handle).decode()
     q = SamtronPlan()
-    q.target_kind = 4
-    lib.gmmvi_train_iter_samtron.argtypes = [C.c_void_p, C.POINTER(SamtronPlan)]
+    q.target.kind = 4
     assert lib.gmmvi_train_iter_samtron(ctx.handle, C.byref(q)) == -2
     assert "talos_model" in ctx.lib.gmmvi_last_error(ctx.handle).decode()
     ctx.sync()
