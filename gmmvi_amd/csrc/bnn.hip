@@ -9,8 +9,8 @@
 //
 // Minibatch stream: row j of sample n's batch has stream position p = n B + j, epoch e = p div T and rank
 // r = p mod T; its data row is pi_{seed,call,e}(r), a 4-round balanced Feistel network on 2h bits (h = ceil(ceil(log2 T)
-// / 2), cycle walking) whose round function is word 0 of Philox4x32-10 (philox.h) with counter (R | i << 24, e, call, 3)
-// (feistel.h).
+// / 2), cycle walking) whose round function is word 0 of Philox4x32-10 (philox.h) with counter (R | i << 24, e, call, 3).
+// feistel.h holds the stream id and the position -> row map for this kernel, bnn_classifier.hip and bnn_mlp.hip.
 // Each lane computes its own index; no sort, no device state.
 //
 // Mapping: one workgroup per sample, one batch row per lane (128 rows per chunk; B > 128 loops over chunks).  The sample's
@@ -25,7 +25,6 @@
 
 namespace {
 constexpr int BNN_THREADS = 128;                       // batch rows per chunk, one per lane
-constexpr uint32_t BNN_STREAM_MINIBATCH = 3;           // stream ids 0-2: oracle/philox.py
 constexpr int BNN_FMAX = 32, BNN_HMAX = 16;
 
 struct BnnShape {
@@ -124,14 +123,11 @@ __global__ __launch_bounds__(BNN_THREADS) void bnn_target_kernel(int F_, int H1_
     __syncthreads();
 
     const float c3 = 2.f * (float)T / (float)B;                        // d(-(T/B) sum r^2) / df_m = (2T/B) r_m
-    const uint64_t base = (uint64_t)n * (uint64_t)B;
-    const uint32_t e_base = (uint32_t)(base / (uint64_t)T), r_base = (uint32_t)(base % (uint64_t)T);
+    const gmmvi_bnn_stream_origin origin = gmmvi_bnn_stream_origin_of(n, B, T);
     for (int c0 = 0; c0 < B; c0 += BNN_THREADS) {
         const int rows = min(BNN_THREADS, B - c0);
         if (t < rows) {
-            uint32_t r = r_base + (uint32_t)(c0 + t), e = e_base;    // r_base + j < 2T since j < B <= T
-            if (r >= (uint32_t)T) { r -= (uint32_t)T; ++e; }
-            const uint32_t row = gmmvi_feistel_permute(r, e, call, BNN_STREAM_MINIBATCH, (uint32_t)T, h, k0, k1);
+            const uint32_t row = gmmvi_bnn_stream_row(origin, c0 + t, T, call, h, k0, k1);
             float x[FM], h1[H1M], h2[H2M];
 #pragma unroll
             for (int i = 0; i < FM; ++i) x[i] = i < F ? X[(size_t)row * F + i] : 0.f;

@@ -40,7 +40,6 @@ constexpr int BC_LDX = BC_KT + 2;                  // forward X tile [128][34]: 
 constexpr int BC_LDW = BC_HP + 16;                 // W1 tile [32][144], h / dZ1 [128][144]: 16 k + i likewise
 constexpr int BC_LDXB = BC_KT + 16;                // backward X tile [128][48]
 constexpr int BC_STAGE = BC_CHUNK * BC_LDX + BC_KT * BC_LDW;       // >= BC_CHUNK * BC_LDXB
-constexpr uint32_t BC_STREAM_MINIBATCH = 3;        // bnn.hip's stream
 static_assert(BC_STAGE >= BC_CHUNK * BC_LDXB, "the backward tile overlays the forward tiles");
 
 // LDS of the predict kernel: W2s [128][16] | b2s [16] | rows [128] | stage; the target kernel adds labels [128] | dl [128][16]
@@ -213,8 +212,7 @@ __global__ __launch_bounds__(BC_THREADS) void bnn_classifier_target_kernel(
     bc_stage_w2(F, H, C, Wn, W2s, b2s, &wsq);
 
     const float coef = -(float)T / (float)B;                           // d(-(T/B) sum CE) / d CE
-    const uint64_t base = (uint64_t)n * (uint64_t)B;
-    const uint32_t e_base = (uint32_t)(base / (uint64_t)T), r_base = (uint32_t)(base % (uint64_t)T);
+    const gmmvi_bnn_stream_origin origin = gmmvi_bnn_stream_origin_of(n, B, T);
     const int j2 = t & 127, ch = t >> 7;                               // dW2: hidden unit j2, classes 8 ch .. 8 ch + 7
     float a2[8], sdl[8], ce_acc = 0.f;
 #pragma unroll
@@ -225,9 +223,7 @@ __global__ __launch_bounds__(BC_THREADS) void bnn_classifier_target_kernel(
         if (t < BC_CHUNK) {
             int row = -1, lab = -1;
             if (t < rows) {
-                uint32_t r = r_base + (uint32_t)(c0 + t), e = e_base;  // r_base + j < 2 T since j < B <= T
-                if (r >= (uint32_t)T) { r -= (uint32_t)T; ++e; }
-                row = (int)gmmvi_feistel_permute(r, e, call, BC_STREAM_MINIBATCH, (uint32_t)T, hbits, k0, k1);
+                row = (int)gmmvi_bnn_stream_row(origin, c0 + t, T, call, hbits, k0, k1);
                 lab = labels[row];
             }
             rows_s[t] = row;

@@ -46,7 +46,6 @@ constexpr int ML_LDH = ML_HP + 4;                  // h / dZ [64][132]: 4 i + k 
 constexpr int ML_LDW = ML_HP + 16;                 // W tile [32][144]: 16 k + i likewise as the forward B operand
 constexpr int ML_LDX = ML_KT + 4;                  // X tile [64][36]
 constexpr int ML_LDO = ML_CP + 4;                  // outputs / d lp / d out [64][20]
-constexpr uint32_t ML_STREAM_MINIBATCH = 3;        // bnn.hip's stream
 constexpr int ML_ACT_LINEAR = 0, ML_ACT_SIGMOID = 1, ML_ACT_RELU = 2, ML_ACT_TANH = 3;
 constexpr int ML_LOSS_MSE = 0, ML_LOSS_CE = 1;
 
@@ -318,8 +317,7 @@ __global__ __launch_bounds__(ML_THREADS) void bnn_mlp_target_kernel(MlpNet net, 
     if (lane == 0) s.red[wave] = ws;
 
     const float coef = -(float)T / (float)B;                           // d(-(T/B) sum loss) / d loss
-    const uint64_t base = (uint64_t)n * (uint64_t)B;
-    const uint32_t e_base = (uint32_t)(base / (uint64_t)T), r_base = (uint32_t)(base % (uint64_t)T);
+    const gmmvi_bnn_stream_origin origin = gmmvi_bnn_stream_origin_of(n, B, T);
     float loss_acc = 0.f;                                              // wave 0
 
     for (int c0 = 0; c0 < B; c0 += ML_CHUNK) {
@@ -327,9 +325,7 @@ __global__ __launch_bounds__(ML_THREADS) void bnn_mlp_target_kernel(MlpNet net, 
         if (t < ML_CHUNK) {
             int row = -1, lab = net.loss == ML_LOSS_CE ? -1 : 0;      // past the batch: no class, label 0.f
             if (t < rows) {
-                uint32_t r = r_base + (uint32_t)(c0 + t), e = e_base;  // r_base + j < 2 T since j < B <= T
-                if (r >= (uint32_t)T) { r -= (uint32_t)T; ++e; }
-                row = (int)gmmvi_feistel_permute(r, e, call, ML_STREAM_MINIBATCH, (uint32_t)T, hbits, k0, k1);
+                row = (int)gmmvi_bnn_stream_row(origin, c0 + t, T, call, hbits, k0, k1);
                 lab = labels[row];                                     // MSE: the bits of the f32 label
             }
             s.rows[t] = row;

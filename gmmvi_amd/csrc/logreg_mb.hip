@@ -29,7 +29,6 @@ constexpr int LRMB_WAVES = 4;
 constexpr int LRMB_CHUNK = 16 * LRMB_WAVES;   // batch rows staged per pass
 constexpr int LRMB_DT = 8;             // 16-column tiles of the gradient
 constexpr int LRMB_DMAX = 16 * LRMB_DT;
-constexpr uint32_t LRMB_STREAM = 4;    // stream ids 0-2: oracle/philox.py, 3: bnn.hip
 
 __host__ __device__ inline int lrmb_ldw(int D) { return ((D + 3) & ~3) + 1; }
 __host__ __device__ inline int lrmb_gld(int D) { return 16 * ((D + 15) / 16) + 1; }
@@ -71,8 +70,8 @@ __global__ __launch_bounds__(256) void logreg_mb_kernel(int D, int T, const floa
     for (int dt = 0; dt < LRMB_DT; ++dt) acc[dt] = lrmb_f32x4{0.f, 0.f, 0.f, 0.f};
     for (int c0 = 0; c0 < B; c0 += LRMB_CHUNK) {
         const int rows = min(LRMB_CHUNK, B - c0);
-        if (t < rows) rows_s[t] = (int)gmmvi_feistel_permute(base + (uint32_t)(c0 + t), 0u, call, LRMB_STREAM, (uint32_t)T, h,
-                                                             k0, k1);
+        if (t < rows) rows_s[t] = (int)gmmvi_feistel_permute(base + (uint32_t)(c0 + t), 0u, call, GMMVI_STREAM_LOGREG_MINIBATCH,
+                                                             (uint32_t)T, h, k0, k1);
         __syncthreads();                                             // also orders the Ws staging before its first read
         for (int idx = t; idx < LRMB_CHUNK * ldw; idx += 256) {
             const int r = idx / ldw, c = idx - r * ldw;

@@ -12,9 +12,9 @@ one launch (csrc/logreg.hip) on the signed matrix A = diag(s) X~.
 ``size_test_set`` rows are held out, and the likelihood of every sample is T times the mean over a batch of ``batch_size``
 training rows.  Upstream reshuffles with TensorFlow's stateful RNG on every call; this build defines the batches instead
 (DESIGN.md 6): call c (the target's call counter) permutes the T training rows by rho_c, the Feistel/Philox permutation of
-bnn.py with key ``seed`` and counter (R | i << 24, 0, c, 4), and sample n takes batch n mod nb, nb = floor(T / B) with
-``use_own_batch_per_sample`` (upstream's advancing ``start``) and 1 without.  ``minibatch_rows`` restates the map in
-NumPy; the device evaluates it in csrc/logreg_mb.hip.
+minibatch_stream.py with key ``seed`` and counter (R | i << 24, 0, c, 4), and sample n takes batch n mod nb, with
+nb = floor(T / B) with ``use_own_batch_per_sample`` (upstream's advancing ``start``) and 1 without.  ``minibatch_rows``
+restates the map in NumPy; the device evaluates it in csrc/logreg_mb.hip.
 
 The datasets do not ship with the package: ``dataset_dir`` (``environment_config["dataset_dir"]``), else the
 ``GMMVI_DATASET_DIR`` environment variable, names a directory with upstream's files ``breast_cancer.data`` and
@@ -26,13 +26,13 @@ import numpy as np
 
 from ... import _lib, hip_ops
 from ...device import get_context
-from .bnn import permute_rows
 from .lnpdf import LNPDF
+from .minibatch_stream import STREAM_LOGREG_MINIBATCH as STREAM_MINIBATCH
+from .minibatch_stream import MinibatchLNPDF, permute_rows
 
 DATASET_FILES = {"breast_cancer": "breast_cancer.data", "german_credit": "german.data-numeric"}
 DATASET_DIR_ENV = "GMMVI_DATASET_DIR"
 PRIOR_MEAN, PRIOR_STD = 0.0, 10.0                   # logistic_regression.py:33-34, :43-44
-STREAM_MINIBATCH = 4                                # Philox stream ids 0-2: samplers, 3: the WINE minibatches
 MAX_DIM_MINIBATCH = 128                             # what csrc/logreg_mb.hip supports
 
 
@@ -164,7 +164,7 @@ def minibatch_rows(seed, call, n, batch_size, num_data, num_batches):
     return permute_rows(seed, call, np.zeros_like(p), p, num_data, stream=STREAM_MINIBATCH)
 
 
-class LogisticRegressionMinibatch(LNPDF):
+class LogisticRegressionMinibatch(MinibatchLNPDF):
     """Minibatch logistic-regression posterior (logistic_regression.py:70-174).
 
     The data matrix is built as for ``LogisticRegression`` (a dataset id with ``data`` or ``dataset_dir``, or ``X`` and
@@ -178,7 +178,7 @@ class LogisticRegressionMinibatch(LNPDF):
 
     def __init__(self, dataset_id=None, batch_size=64, size_test_set=0, use_own_batch_per_sample=True, data=None,
                  dataset_dir=None, X=None, labels=None, seed=0, prior_mean=PRIOR_MEAN, prior_std=PRIOR_STD):
-        super().__init__(use_log_density_and_grad=True)
+        super().__init__(seed)
         A = build_data_matrix(dataset_id, data, dataset_dir, X, labels)
         size_test_set = int(size_test_set)
         if not 0 <= size_test_set < A.shape[0]:
@@ -196,9 +196,7 @@ class LogisticRegressionMinibatch(LNPDF):
         self.batch_size, self.size_test_set = int(batch_size), size_test_set
         self.use_own_batch_per_sample = bool(use_own_batch_per_sample)
         self.num_batches = num_batches(self.num_data, self.batch_size, self.use_own_batch_per_sample)
-        self.seed = int(seed)
         self.prior_mean, self.prior_std = float(prior_mean), float(prior_std)
-        self._call = 0
         self.ctx = get_context()
         self._A_dev = self.ctx.asarray(self.A)
 
@@ -206,26 +204,12 @@ class LogisticRegressionMinibatch(LNPDF):
     def num_data(self):
         return int(self.A.shape[0])
 
-    @property
-    def call_count(self):
-        return self._call
-
     def get_num_dimensions(self):
         return int(self.A.shape[1])
 
-    def _evaluate(self, x, want_grad):
-        x = self.ctx.asarray(x)
-        lp, grad = hip_ops.target_logreg_mb(self.ctx, self._A_dev, self.batch_size, self.num_batches, self.seed, self._call,
-                                            self.prior_mean, self.prior_std, x, want_grad=want_grad)
-        if x.shape[0] >= 1:
-            self._call += 1
-        return lp, grad
-
-    def log_density(self, x):
-        return self._evaluate(x, False)[0]
-
-    def log_density_and_grad(self, x):
-        return self._evaluate(x, True)
+    def _launch(self, x, call, want_grad):
+        return hip_ops.target_logreg_mb(self.ctx, self._A_dev, self.batch_size, self.num_batches, self.seed, call,
+                                        self.prior_mean, self.prior_std, x, want_grad=want_grad)
 
     def log_density_fb(self, x):
         """The full-batch posterior on the training rows (csrc/logreg.hip); leaves the call counter alone."""

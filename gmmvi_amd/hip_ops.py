@@ -105,19 +105,53 @@ def target_logreg(ctx, A, prior_mean, prior_std, x, want_grad=True):
     return lp, grad
 
 
+def _minibatch_target(ctx, entry, head, seed, call, tail, x, d, want_grad):
+    """lp [n] and grad [n, d] of a minibatch target: entry(handle, *head, seed, call, *tail, x, n, lp, grad) with the seed
+    and the call counter cut to the 64 and 32 bits the stream takes."""
+    n = x.shape[0]
+    _req(x, (n, d), name="x")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(entry(ctx.handle, *head, int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, *tail, x.ptr, n, lp.ptr,
+                        None if grad is None else grad.ptr))
+    return lp, grad
+
+
+def _predict_slabs(ctx, entry, head, W, d, X, out_shape):
+    """Forward pass of every weight vector W [S, d] on every row X [M, F] -> out [S, M, ...]: entry(handle, *head, W, S, X, M,
+    out) over slabs of W, since the kernels' grid takes at most 65535 weight vectors per launch."""
+    s, (m, f) = W.shape[0], X.shape
+    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
+    out = ctx.empty((s, m) + tuple(out_shape))
+    if m > 0:
+        for s0 in range(0, s, 65535):
+            s1 = min(s, s0 + 65535)
+            ctx.check(entry(ctx.handle, *head, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m, out.rows(s0, s1).ptr))
+    return out
+
+
 def target_logreg_mb(ctx, A, batch_size, num_batches, seed, call, prior_mean, prior_std, x, want_grad=True):
     """Minibatch logistic-regression posterior (csrc/logreg_mb.hip).  A: [T, D] signed training rows; sample n takes batch
     n mod num_batches of the permutation of (seed, call).  -> (lp [n], grad [n, D])."""
     t, d = A.shape
-    n = x.shape[0]
-    _req(A, (t, d), name="A"); _req(x, (n, d), name="x")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0:
-        ctx.check(ctx.lib.gmmvi_target_logreg_mb(ctx.handle, d, t, A.ptr, int(batch_size), int(num_batches),
-                                                 int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, float(prior_mean),
-                                                 float(prior_std), x.ptr, n, lp.ptr, None if grad is None else grad.ptr))
-    return lp, grad
+    _req(A, (t, d), name="A")
+    return _minibatch_target(ctx, ctx.lib.gmmvi_target_logreg_mb, (d, t, A.ptr, int(batch_size), int(num_batches)), seed, call,
+                             (float(prior_mean), float(prior_std)), x, d, want_grad)
+
+
+def mlp_num_parameters(num_features, hidden_units, num_outputs=1):
+    """Per layer W [in, out], then b [out], over num_features -> hidden_units ... -> num_outputs (1 for a regressor, the
+    number of classes for a classifier)."""
+    d, last = 0, int(num_features)
+    for width in [int(h) for h in hidden_units] + [int(num_outputs)]:
+        d += last * width + width
+        last = width
+    return d
+
+
+def bnn_classifier_num_parameters(num_features, hidden, num_classes):
+    return mlp_num_parameters(num_features, (hidden,), num_classes)
 
 
 def target_bnn(ctx, X, y, hidden_units, seed, call, batch_size, likelihood_scaling, prior_std, x, want_grad=True):
@@ -125,37 +159,17 @@ def target_bnn(ctx, X, y, hidden_units, seed, call, batch_size, likelihood_scali
     hidden_units (H1, H2); the minibatch rows come from the stream of (seed, call).  -> (lp [n], grad [n, D])."""
     t, f = X.shape
     h1, h2 = (int(h) for h in hidden_units)
-    d = f * h1 + h1 + h1 * h2 + h2 + h2 + 1
-    n = x.shape[0]
-    _req(X, (t, f), name="X"); _req(y, (t,), name="y"); _req(x, (n, d), name="x")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0:
-        ctx.check(ctx.lib.gmmvi_target_bnn(ctx.handle, f, h1, h2, t, X.ptr, y.ptr, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                           int(call) & 0xFFFFFFFF, int(batch_size), float(likelihood_scaling),
-                                           float(prior_std), x.ptr, n, lp.ptr, None if grad is None else grad.ptr))
-    return lp, grad
+    _req(X, (t, f), name="X"); _req(y, (t,), name="y")
+    return _minibatch_target(ctx, ctx.lib.gmmvi_target_bnn, (f, h1, h2, t, X.ptr, y.ptr), seed, call,
+                             (int(batch_size), float(likelihood_scaling), float(prior_std)), x,
+                             mlp_num_parameters(f, (h1, h2)), want_grad)
 
 
 def bnn_predict(ctx, hidden_units, W, X):
     """Network outputs of every weight vector on every row (csrc/bnn.hip), forward only.  W: [S, D], X: [M, F] -> [S, M]."""
-    m, f = X.shape
+    _, f = X.shape
     h1, h2 = (int(h) for h in hidden_units)
-    d = f * h1 + h1 + h1 * h2 + h2 + h2 + 1
-    s = W.shape[0]
-    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
-    out = ctx.empty((s, m))
-    if m > 0:
-        for s0 in range(0, s, 65535):                   # the kernel's grid takes at most 65535 weight vectors per launch
-            s1 = min(s, s0 + 65535)
-            ctx.check(ctx.lib.gmmvi_bnn_predict(ctx.handle, f, h1, h2, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m,
-                                                out.rows(s0, s1).ptr))
-    return out
-
-
-def bnn_classifier_num_parameters(num_features, hidden, num_classes):
-    f, h, c = int(num_features), int(hidden), int(num_classes)
-    return f * h + h + h * c + c
+    return _predict_slabs(ctx, ctx.lib.gmmvi_bnn_predict, (f, h1, h2), W, mlp_num_parameters(f, (h1, h2)), X, ())
 
 
 def target_bnn_classifier(ctx, X, labels, hidden, num_classes, seed, call, batch_size, likelihood_scaling, prior_std, x,
@@ -165,47 +179,21 @@ def target_bnn_classifier(ctx, X, labels, hidden, num_classes, seed, call, batch
     (seed, call).  -> (lp [n], grad [n, D])."""
     t, f = X.shape
     h, c = int(hidden), int(num_classes)
-    d = bnn_classifier_num_parameters(f, h, c)
-    n = x.shape[0]
-    _req(X, (t, f), name="X"); _req(labels, (t,), I32, name="labels"); _req(x, (n, d), name="x")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0:
-        ctx.check(ctx.lib.gmmvi_target_bnn_classifier(ctx.handle, f, h, c, t, X.ptr, labels.ptr,
-                                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF,
-                                                      int(batch_size), float(likelihood_scaling), float(prior_std), x.ptr,
-                                                      n, lp.ptr, None if grad is None else grad.ptr))
-    return lp, grad
+    _req(X, (t, f), name="X"); _req(labels, (t,), I32, name="labels")
+    return _minibatch_target(ctx, ctx.lib.gmmvi_target_bnn_classifier, (f, h, c, t, X.ptr, labels.ptr), seed, call,
+                             (int(batch_size), float(likelihood_scaling), float(prior_std)), x,
+                             mlp_num_parameters(f, (h,), c), want_grad)
 
 
 def bnn_classifier_predict(ctx, hidden, num_classes, W, X):
     """Logits of every weight vector on every row (csrc/bnn_classifier.hip), forward only.  W: [S, D], X: [M, F]
     -> [S, M, C]."""
-    m, f = X.shape
-    h, c = int(hidden), int(num_classes)
-    d = bnn_classifier_num_parameters(f, h, c)
-    s = W.shape[0]
-    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
-    out = ctx.empty((s, m, c))
-    if m > 0:
-        for s0 in range(0, s, 65535):                   # the kernel's grid takes at most 65535 weight vectors per launch
-            s1 = min(s, s0 + 65535)
-            ctx.check(ctx.lib.gmmvi_bnn_classifier_predict(ctx.handle, f, h, c, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m,
-                                                           out.rows(s0, s1).ptr))
-    return out
+    (_, f), h, c = X.shape, int(hidden), int(num_classes)
+    return _predict_slabs(ctx, ctx.lib.gmmvi_bnn_classifier_predict, (f, h, c), W, mlp_num_parameters(f, (h,), c), X, (c,))
 
 
 MLP_MAX_FEATURES, MLP_MAX_HIDDEN, MLP_MAX_HIDDEN_LAYERS = 1024, 128, _lib.MLP_MAX_LAYERS - 1     # csrc/bnn_mlp.hip
 MLP_MIN_CLASSES, MLP_MAX_CLASSES, MLP_MAX_BATCH = 2, 16, 1024
-
-
-def mlp_num_parameters(num_features, hidden_units, num_outputs=1):
-    """Per layer W [in, out], then b [out], over num_features -> hidden_units ... -> num_outputs."""
-    d, last = 0, int(num_features)
-    for width in [int(h) for h in hidden_units] + [int(num_outputs)]:
-        d += last * width + width
-        last = width
-    return d
 
 
 def mlp_desc(num_features, hidden_units, activations, loss, num_outputs=1):
@@ -255,38 +243,24 @@ def target_mlp(ctx, X, y, hidden_units, activations, loss, num_outputs, seed, ca
     from the stream of (seed, call).  -> (lp [n], grad [n, D])."""
     t, f = X.shape
     desc = mlp_desc(f, hidden_units, activations, loss, num_outputs)
-    d = mlp_num_parameters(f, hidden_units, num_outputs)
-    n = x.shape[0]
-    _req(X, (t, f), name="X"); _req(y, (t,), F32 if loss == "mse" else I32, name="y"); _req(x, (n, d), name="x")
+    _req(X, (t, f), name="X"); _req(y, (t,), F32 if loss == "mse" else I32, name="y")
     if not 1 <= int(batch_size) <= min(t, MLP_MAX_BATCH):
         raise ValueError(f"batch_size must lie in [1, {min(t, MLP_MAX_BATCH)}] (the training-set size, at most "
                          f"{MLP_MAX_BATCH}), got {batch_size}")
     if not prior_std > 0:
         raise ValueError("prior_std must be positive")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0:
-        ctx.check(ctx.lib.gmmvi_target_mlp(ctx.handle, desc, t, X.ptr, y.ptr, int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                           int(call) & 0xFFFFFFFF, int(batch_size), float(likelihood_scaling),
-                                           float(prior_std), x.ptr, n, lp.ptr, None if grad is None else grad.ptr))
-    return lp, grad
+    return _minibatch_target(ctx, ctx.lib.gmmvi_target_mlp, (desc, t, X.ptr, y.ptr), seed, call,
+                             (int(batch_size), float(likelihood_scaling), float(prior_std)), x,
+                             mlp_num_parameters(f, hidden_units, num_outputs), want_grad)
 
 
 def mlp_predict(ctx, hidden_units, activations, loss, num_outputs, W, X):
     """Network outputs of every weight vector on every row (csrc/bnn_mlp.hip), forward only.  W: [S, D], X: [M, F]
     -> [S, M] ("mse") or logits [S, M, C]."""
-    m, f = X.shape
+    _, f = X.shape
     desc = mlp_desc(f, hidden_units, activations, loss, num_outputs)
-    d = mlp_num_parameters(f, hidden_units, num_outputs)
-    s = W.shape[0]
-    _req(W, (s, d), name="W"); _req(X, (m, f), name="X")
-    out = ctx.empty((s, m) if loss == "mse" else (s, m, int(num_outputs)))
-    if m > 0:
-        for s0 in range(0, s, 65535):                   # the kernel's grid takes at most 65535 weight vectors per launch
-            s1 = min(s, s0 + 65535)
-            ctx.check(ctx.lib.gmmvi_mlp_predict(ctx.handle, desc, W.rows(s0, s1).ptr, s1 - s0, X.ptr, m,
-                                                out.rows(s0, s1).ptr))
-    return out
+    return _predict_slabs(ctx, ctx.lib.gmmvi_mlp_predict, (desc,), W, mlp_num_parameters(f, hidden_units, num_outputs), X,
+                          () if loss == "mse" else (int(num_outputs),))
 
 
 TALOS_DIM = 34                                         # csrc/talos.hip: 28 joints, base position, roll / pitch / yaw

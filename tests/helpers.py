@@ -182,3 +182,15 @@ def score_elbo(target, log_weights, means, chols, temperature=1.0, num_samples=2
     x, _ = m.sample(num_samples, seed, 0)
     per = target.log_density(x) - temperature * m.log_density(x)
     return float(np.mean(per)), float(np.std(per) / np.sqrt(num_samples))
+
+
+class HostContext:
+    """Stands in for the device context where a test only exercises host logic."""
+
+    def asarray(self, x, dtype=np.float32):
+        return np.asarray(x, dtype)
+
+
+def use_host_context(monkeypatch, module):
+    """Targets built from ``module`` get a HostContext instead of the device's context."""
+    monkeypatch.setattr(module, "get_context", lambda: HostContext())

@@ -10,22 +10,16 @@ import pytest
 from bnn_classifier_ref import (BNNClassifierRef, literal_cross_entropy, literal_forward, log_softmax, num_parameters,
                                 offsets, separable_data, unpack, write_mnist_dir)
 from bnn_ref import stream_rows
+from helpers import use_host_context
 
 from gmmvi_amd.experiments.target_distributions import bnn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-class _HostContext:
-    """Stands in for the device context where a test only exercises host logic."""
-
-    def asarray(self, x, dtype=np.float32):
-        return np.asarray(x, dtype)
-
-
 @pytest.fixture
 def host_ctx(monkeypatch):
-    monkeypatch.setattr(bnn, "get_context", lambda: _HostContext())
+    use_host_context(monkeypatch, bnn)
 
 
 # ---- the fp64 reference ------------------------------------------------------------------------------------------------

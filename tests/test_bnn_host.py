@@ -7,20 +7,14 @@ import numpy as np
 import pytest
 
 from bnn_ref import GOLDEN, BNNRef, literal_forward, literal_mse, load_wine, stream_rows, unpack, write_dataset_dir
+from helpers import use_host_context
 
 from gmmvi_amd.experiments.target_distributions import bnn
 
 
-class _HostContext:
-    """Stands in for the device context where a test only exercises host logic."""
-
-    def asarray(self, x, dtype=np.float32):
-        return np.asarray(x, dtype)
-
-
 @pytest.fixture
 def host_ctx(monkeypatch):
-    monkeypatch.setattr(bnn, "get_context", lambda: _HostContext())
+    use_host_context(monkeypatch, bnn)
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,7 @@ import bnn_mlp_cases as cases
 from bnn_classifier_ref import BNNClassifierRef
 from bnn_mlp_ref import BNNMlpRef, num_parameters, unpack
 from bnn_ref import BNNRef, stream_rows
+from helpers import use_host_context
 
 from gmmvi_amd.experiments.target_distributions import bnn
 
@@ -18,16 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MSE, CE = cases.MSE, cases.CE
 
 
-class _HostContext:
-    """Stands in for the device context where a test only exercises host logic."""
-
-    def asarray(self, x, dtype=np.float32):
-        return np.asarray(x, dtype)
-
-
 @pytest.fixture
 def host_ctx(monkeypatch):
-    monkeypatch.setattr(bnn, "get_context", lambda: _HostContext())
+    use_host_context(monkeypatch, bnn)
 
 
 # ---- the fp64 reference ------------------------------------------------------------------------------------------------

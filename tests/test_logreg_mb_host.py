@@ -7,7 +7,7 @@ import pytest
 from logreg_mb_ref import LogRegMbRef, batch_rows, rho, upstream_start_loop_rows
 from logreg_ref import LogRegRef, load_tables
 
-from gmmvi_amd.experiments.target_distributions import bnn
+from gmmvi_amd.experiments.target_distributions import minibatch_stream
 from gmmvi_amd.experiments.target_distributions import logistic_regression as lr
 
 CASES = [(seed, call, T, B, own)
@@ -57,9 +57,9 @@ def test_batches_of_a_call_are_disjoint_and_vary_with_call_and_seed(T, B):
 
 def test_stream_ids_are_separate_and_wine_keeps_its_own():
     p = np.arange(569)
-    wine = bnn.permute_rows(7, 2, np.zeros_like(p), p, 569)
-    np.testing.assert_array_equal(wine, bnn.permute_rows(7, 2, np.zeros_like(p), p, 569, stream=3))
-    mb = bnn.permute_rows(7, 2, np.zeros_like(p), p, 569, stream=lr.STREAM_MINIBATCH)
+    wine = minibatch_stream.permute_rows(7, 2, np.zeros_like(p), p, 569)
+    np.testing.assert_array_equal(wine, minibatch_stream.permute_rows(7, 2, np.zeros_like(p), p, 569, stream=3))
+    mb = minibatch_stream.permute_rows(7, 2, np.zeros_like(p), p, 569, stream=lr.STREAM_MINIBATCH)
     np.testing.assert_array_equal(mb, rho(7, 2, p, 569))
     assert np.mean(mb != wine) > 0.9
 
