@@ -15,6 +15,7 @@ MORE_REGISTER_MAX_DIM = 21     # gmmvi_more: register-resident ridge system up t
 MORE_BLOCKED_MIN_DIM, MORE_BLOCKED_MAX_DIM = 64, 128   # gmmvi_more_blocked: MORE from the blocked component layout
 MORE_DIAG_MAX_DIM = 1024       # gmmvi_more_diag: MORE for diagonal-covariance mixtures (F = 2 D + 1 features)
 MAX_DIM_BLOCKED = 512          # dense [K, D, D] factors (blocked kernels) exist up to here
+CUSTOM_STAGED_MAX_DIM = 120    # gmmvi_target_custom: the staged (LDS) route up to here, the direct route above
 MAX_DIM_DIAG = 131072          # diagonal-covariance mixtures: csrc/diag_sweep.hip, csrc/diag.hip
 BLOCKED_ABOVE_DEFAULT = 50     # csrc/blocked.h: D > 50 runs the blocked (MFMA) kernels
 
@@ -74,7 +75,7 @@ class TargetSpec(C.Structure):
     _fields_ = [("kind", _i32), ("mix_family", _i32), ("mix_K", _i32), ("mix_nu", _f), ("mix_packed", _p), ("mix_logw", _p),
                 ("planar_prior_std", _p), ("planar_goals", _p), ("planar_goals_count", _i32), ("planar_likelihood_std", _f),
                 ("logreg_A", _p), ("logreg_M", _i32), ("logreg_prior_mean", _f), ("logreg_prior_std", _f),
-                ("talos_model", _p), ("talos_context", _p)]
+                ("talos_model", _p), ("talos_context", _p), ("custom", _p), ("custom_params", _p)]
 
 
 class StepsizeRule(C.Structure):
@@ -178,6 +179,10 @@ _PROTOS = {
     "gmmvi_mlp_predict": (_i, [_p, C.POINTER(MlpDesc), _p, _i, _p, _i, _p]),
     "gmmvi_target_talos": (_i, [_p, _p, _p, _p, _i, _p, _p]),
     "gmmvi_talos_fk": (_i, [_p, _p, _p, _i, _p, _p]),
+    "gmmvi_custom_target_check": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
+    "gmmvi_custom_target_compile": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
+    "gmmvi_custom_target_release": (_i, [_p, _p]),
+    "gmmvi_target_custom": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),

@@ -57,6 +57,7 @@ void gmmvi_ctx_destroy(gmmvi_ctx* ctx) {
         (void)hipStreamSynchronize(ctx->stream);
         (void)hipStreamDestroy(ctx->stream);
     }
+    gmmvi_custom_targets_destroy(ctx);
     if (ctx->ws) (void)hipFree(ctx->ws);
     if (ctx->arena) (void)hipFree(ctx->arena);
     if (ctx->bimg) (void)hipFree(ctx->bimg);

@@ -68,6 +68,7 @@ struct gmmvi_ctx {
     void* defer_ws = nullptr;    // partials of a deferred merge (ctx->ws is reused by the launches in between)
     size_t defer_bytes = 0;
     void* comm = nullptr;        // ncclComm_t
+    std::vector<gmmvi_custom_target*> custom_targets;   // loaded user-defined targets (custom_target.hip), released with the context
     int n_ranks = 1, rank = 0;
     int num_cus = 256;
     unsigned func_attr_done = 0; // bits: per-device kernel attributes (dynamic LDS above 64 KB) already set for this context's device
@@ -118,6 +119,8 @@ inline int gmmvi_fail(gmmvi_ctx* ctx, int code, const std::string& msg) {
 #define GMMVI_LAUNCH_CHECK(ctx) GMMVI_HIP_CHECK(ctx, hipGetLastError())
 
 int gmmvi_ws_reserve(gmmvi_ctx* ctx, size_t nbytes);
+// custom_target.hip: unloads every user-defined target of the context (gmmvi_ctx_destroy)
+void gmmvi_custom_targets_destroy(gmmvi_ctx* ctx);
 // density.hip: component blocks in the register-path layout (Pack<padded D>, D <= 64) regardless of the blocked threshold
 int gmmvi_pack_register_layout(gmmvi_ctx* ctx, int K, int D, const float* means_dev, const float* chols_dev, float* packed_dev);
 // sampling.hip: gmmvi_sample_components with a caller-known bound on the samples per component (fewer empty workgroups)

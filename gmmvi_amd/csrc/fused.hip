@@ -69,13 +69,15 @@ static void drop_pending(gmmvi_ctx* ctx) {
 }
 
 static int check_target(gmmvi_ctx* ctx, const gmmvi_target_spec& t, int D) {
-    if (!((t.kind >= 0 && t.kind <= 2) || t.kind == 4))
+    if (!((t.kind >= 0 && t.kind <= 2) || t.kind == 4 || t.kind == 5))
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: target_kind " + std::to_string(t.kind) +
-                                                  " (0 mixture, 1 planar robot, 2 logistic regression, 4 Talos)");
+                                                  " (0 mixture, 1 planar robot, 2 logistic regression, 4 Talos, 5 user-defined)");
     if (t.kind == 2 && !(t.logreg_A && t.logreg_M >= 1 && t.logreg_prior_std > 0.f))
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: target_kind 2 needs logreg_A, logreg_M >= 1 and logreg_prior_std > 0");
     if (t.kind == 4 && !(t.talos_model && t.talos_context && D == 34))
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: target_kind 4 needs talos_model, talos_context and D == 34");
+    if (t.kind == 5 && !t.custom)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: target_kind 5 needs custom (gmmvi_custom_target_compile)");
     return GMMVI_OK;
 }
 
@@ -85,6 +87,7 @@ static int eval_target(gmmvi_ctx* ctx, const gmmvi_target_spec& t, int D, const 
                                            x, n, lp, grad);
         case 2: return gmmvi_target_logreg(ctx, D, t.logreg_M, t.logreg_A, t.logreg_prior_mean, t.logreg_prior_std, x, n, lp, grad);
         case 4: return gmmvi_target_talos(ctx, t.talos_model, t.talos_context, x, n, lp, grad);
+        case 5: return gmmvi_target_custom(ctx, t.custom, D, t.custom_params, x, n, lp, grad, 0);   // (no riders, no merge: flushed behind it)
         default: {
             SweepScope sweep(ctx, "sweep_target", false);
             return gmmvi_mixture_eval(ctx, t.mix_family, t.mix_nu, t.mix_K, D, t.mix_packed, t.mix_logw, x, n, nullptr, lp, grad);

@@ -1,0 +1,71 @@
+"""User-defined target evaluated on the device (no upstream counterpart; upstream's custom targets are Python subclasses of
+LNPDF, examples/4_gmmvi_runner_with_custom_environments.py).
+
+The target is HIP source text that defines
+
+    __device__ float gmmvi_user_target(const float* x, int D, const float* params, float* grad);
+
+(contract: include/gmmvi_hip.h).  It is compiled at run time for the device of the context and evaluated by the
+library's wrapper kernels (csrc/custom_target.hip): the samples never leave the device, and the single-call and the sharded
+iteration take it as target kind 5.
+"""
+import numpy as np
+
+from ... import _lib, hip_ops
+from ...device import get_context
+from .lnpdf import LNPDF
+
+
+class DeviceLNPDF(LNPDF):
+    """``DeviceLNPDF(source, num_dimensions, params=None, has_gradient=True)``; pass it as ``config['target_fn']``.
+
+    params: the target's own numbers (1-D, fp32 on the device; ``None``: the function gets a null pointer).
+    has_gradient=False: the source ignores ``grad``.  The object then implements ``log_density`` only, exactly like a Python
+    black-box target: it runs under the gradient-free estimators (MORE), and a first-order estimator raises the
+    ``NotImplementedError`` of ``LNPDF.log_density_and_grad``."""
+
+    def __new__(cls, source=None, num_dimensions=None, params=None, has_gradient=True):
+        if cls is DeviceLNPDF and has_gradient:
+            cls = _DeviceLNPDFWithGradient
+        return object.__new__(cls)
+
+    def __init__(self, source, num_dimensions, params=None, has_gradient=True):
+        super().__init__(use_log_density_and_grad=True)
+        if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
+            raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
+        if int(num_dimensions) > _lib.MAX_DIM_DIAG:
+            raise ValueError(f"num_dimensions must be <= {_lib.MAX_DIM_DIAG}, got {num_dimensions}")
+        if params is not None:
+            params = np.ascontiguousarray(np.asarray(params.numpy() if hasattr(params, "numpy") else params), np.float32)
+            if params.ndim != 1:
+                raise ValueError(f"params must be one-dimensional, got shape {params.shape}")
+        self.ctx = get_context()
+        self.source = str(source)
+        self.has_gradient = bool(has_gradient)
+        self._num_dimensions = int(num_dimensions)
+        self._params_dev = None if params is None or params.size == 0 else self.ctx.asarray(params)
+        self._handle = hip_ops.custom_target_compile(self.ctx, self.source)
+
+    def get_num_dimensions(self):
+        return self._num_dimensions
+
+    def _x(self, x):
+        x = self.ctx.asarray(x)
+        if len(x.shape) != 2 or x.shape[1] != self._num_dimensions:
+            raise ValueError(f"samples: expected [n, {self._num_dimensions}], got {x.shape}")
+        return x
+
+    def log_density(self, x):
+        return hip_ops.target_custom(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=False)[0]
+
+
+class _DeviceLNPDFWithGradient(DeviceLNPDF):
+    """What ``DeviceLNPDF(..., has_gradient=True)`` constructs: the gradient call and the descriptor of the plans."""
+
+    def log_density_and_grad(self, x):
+        return hip_ops.target_custom(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=True)
+
+    def _fast_path_target(self):
+        """Descriptor for the single-call and the sharded iteration (optimization/fused.py, sharded.py)."""
+        return _lib.TargetSpec(kind=5, custom=self._handle.ptr,
+                               custom_params=None if self._params_dev is None else self._params_dev.ptr)

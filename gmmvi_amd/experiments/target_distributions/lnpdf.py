@@ -3,7 +3,8 @@
 User targets subclass ``LNPDF`` exactly as with the reference.  Arrays crossing this boundary are ``DeviceArray``s
 (``.numpy()`` like a tf.Tensor) on the way in; NumPy arrays or anything with ``.numpy()`` on the way out.  There is
 no automatic differentiation in this build: a first-order estimator (Stein) needs ``log_density_and_grad``; the
-built-in targets implement it with analytic-gradient kernels.
+built-in targets implement it with analytic-gradient kernels.  A target that should run on the device instead of the host
+is written as a HIP device function: ``device_lnpdf.DeviceLNPDF``.
 """
 
 

@@ -92,6 +92,62 @@ def target_planar(ctx, prior_std, goals, likelihood_std, x, want_grad=True):
     return lp, grad
 
 
+def custom_target_check(source, arch="gfx950"):
+    """Compiles a user target's source behind the wrapper kernels for ``arch`` (csrc/custom_target.hip) without a device.
+    -> (status, compiler log): 0 when it compiles, GMMVI_ERR_ARG (-2) with the log otherwise."""
+    import ctypes as C
+    log = C.create_string_buffer(1 << 16)
+    rc = _lib.load().gmmvi_custom_target_check(str(source).encode(), str(arch).encode(), log, len(log))
+    return int(rc), log.value.decode(errors="replace")
+
+
+class CustomTarget:
+    """A compiled user target of a context (gmmvi_custom_target); released with the object."""
+
+    def __init__(self, ctx, handle):
+        self.ctx, self.handle = ctx, handle
+
+    @property
+    def ptr(self):
+        return self.handle.value
+
+    def __del__(self):
+        try:
+            if self.handle:
+                self.ctx.lib.gmmvi_custom_target_release(self.ctx.handle, self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+
+def custom_target_compile(ctx, source):
+    """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  A source that does
+    not compile raises GmmviError with the compiler log."""
+    import ctypes as C
+    h = C.c_void_p()
+    ctx.check(ctx.lib.gmmvi_custom_target_compile(ctx.handle, str(source).encode(), C.byref(h)))
+    return CustomTarget(ctx, h)
+
+
+def target_custom(ctx, handle, params, x, want_grad=True, route=0):
+    """User target ``handle`` on x [n, D] (csrc/custom_target.hip).  params: the target's 1-D device array or None; route: 0
+    auto, 1 staged (LDS), 2 direct.  -> (lp [n], grad [n, D] or None)."""
+    if not isinstance(handle, CustomTarget):
+        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
+    n, d = x.shape
+    _req(x, (n, d), name="x")
+    if params is not None:
+        if len(params.shape) != 1:
+            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
+        _req(params, params.shape, name="params")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_custom(ctx.handle, handle.handle, d, None if params is None else params.ptr, x.ptr, n,
+                                              lp.ptr, None if grad is None else grad.ptr, int(route)))
+    return lp, grad
+
+
 def target_logreg(ctx, A, prior_mean, prior_std, x, want_grad=True):
     """Logistic-regression posterior (csrc/logreg.hip).  A: [M, D] signed data matrix diag(s) X~.  -> (lp [n], grad [n, D])."""
     m, d = A.shape

@@ -9,7 +9,8 @@ Sample reuse (``ratio_reused_samples_to_desired`` > 0, the reference's default `
 of new samples per component follows from the effective sample sizes of the reused ones (sample_selector.py:160-202);
 those K numbers are computed on the device by the same three launches the selector module issues and read back (the one
 host synchronisation of such an iteration, as upstream's ``tf.floor`` implies), then the rest of the iteration is the one
-C call.  Anything else -- MORE, direct/iBLR updaters, own-samples-only, user targets, diagonal GMMs, want_info, an
+C call.  Anything else -- MORE, direct/iBLR updaters, own-samples-only, host-side user targets (a DeviceLNPDF is target kind
+5 and stays on this path), diagonal GMMs, want_info, an
 iteration in which the database has to be thinned out -- takes the modular path.  Disable with ``GMMVI_FAST_PATH=0``.
 """
 import ctypes as C

@@ -91,7 +91,9 @@ class MoreNgEstimator(NgEstimator):
     and one fp64 Cholesky solve per component (csrc/more.hip): register-resident up to D = 21, tiled above (D <= 63; components of a blocked-path dimension are re-packed for the call).  64 <= D <= 128: csrc/more_blocked.hip
     (whitening from the dense L^-1 of the blocked component blocks, Cholesky spread over the chip)."""
 
-    uses_target_gradients = True       # upstream's MORE asks the selector for gradients (:291) although it does not read them
+    # upstream's MORE asks the selector for gradients (:291) although it does not read them (:296-299): a target whose class
+    # implements log_density alone runs under it (SampleSelector.get_target_grads); one with log_density_and_grad keeps that call
+    uses_target_gradients = False
 
     def __init__(self, temperature, model, only_use_own_samples: bool, initial_l2_regularizer: float,
                  use_self_normalized_importance_weights: bool):

@@ -291,6 +291,43 @@ int gmmvi_target_talos(gmmvi_ctx* ctx, const float* model_dev, const float* cont
  * world position (3) and rotation (9, row-major); com_out_dev[N,3] the world centre of mass of the 37 path links. */
 int gmmvi_talos_fk(gmmvi_ctx* ctx, const float* model_dev, const float* X_dev, int N, float* poses_out_dev, float* com_out_dev);
 
+/* ---- user-defined device targets -------------------------------------------------------------------------------------------
+ * The counterpart of subclassing LNPDF (target_distributions/lnpdf.py, examples/4_gmmvi_runner_with_custom_environments.py)
+ * at device speed: the target is HIP source text, compiled at run time (hiprtc, loaded on first use; without libhiprtc.so the
+ * calls below return GMMVI_ERR_HIP and name it) for the device of the context and evaluated by wrapper kernels of this
+ * library (csrc/custom_target_wrap.inc).  The contract: the source defines exactly one function
+ *
+ *     __device__ float gmmvi_user_target(const float* x, int D, const float* params, float* grad);
+ *
+ *   - x: the sample's row of D floats; params: the target's own device array (params_dev below; NULL when it has none);
+ *   - grad: NULL, or the sample's gradient row.  With grad == NULL the function returns the log density and writes nothing;
+ *     with a row it also writes ALL D entries of the gradient of the log density;
+ *   - the function is pure per sample: no barriers, no LDS of its own, no atomics, no writes other than grad[0 .. D);
+ *   - it may define helper __device__ functions and constants beside it; the text is compiled with -O3 -std=c++17, without
+ *     fast-math, and may not define names that begin with gmmvi_ other than gmmvi_user_target.
+ * A function that breaks the contract (reads or writes out of bounds, synchronises, never returns) can fault or hang the
+ * device, like any kernel: the library cannot check it.
+ * Two routes evaluate it.  Staged (D <= GMMVI_CUSTOM_STAGED_MAX_DIM): a wavefront copies 64 consecutive rows of X into LDS,
+ * every lane calls the function on its LDS row with an LDS gradient row, and the gradient tile is written back as one
+ * coalesced stream.  Direct (D <= GMMVI_MAX_DIM_DIAG): the lane is the sample, x and grad are the global rows. */
+#define GMMVI_CUSTOM_STAGED_MAX_DIM 120   /* two [64][D | 1] fp32 images: 61952 B of LDS at D = 120 */
+typedef struct gmmvi_custom_target gmmvi_custom_target;
+/* Compiles source + wrapper kernels for `arch` ("gfx950") and discards the code object.  Needs no device and no context.
+ * log_out[log_cap] (may be NULL) receives the compiler log, cut to fit.  0; GMMVI_ERR_ARG: the source does not compile (a
+ * source without gmmvi_user_target: the log names it); the text is also in gmmvi_last_error(NULL). */
+int gmmvi_custom_target_check(const char* source, const char* arch, char* log_out, size_t log_cap);
+/* Compiles for the context's device (--offload-arch=<its gcnArchName>) and loads the code object.  The context keeps its loaded
+ * targets keyed by a hash of the source: the same source again returns the same handle (counted; one release per compile).
+ * A compile error: GMMVI_ERR_ARG, the compiler log in gmmvi_last_error.  Everything left is released with the context. */
+int gmmvi_custom_target_compile(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out);
+int gmmvi_custom_target_release(gmmvi_ctx* ctx, gmmvi_custom_target* target);    /* waits for the stream; NULL is a no-op */
+/* lp[n] = gmmvi_user_target(X[n], D, params, grad ? grad[n] : NULL).  X_dev[N,D], lp_out_dev[N], grad_out_dev[N,D] or NULL
+ * (values only).  route: 0 auto (staged up to GMMVI_CUSTOM_STAGED_MAX_DIM, direct above), 1 staged, 2 direct.  N >= 1,
+ * 1 <= D <= GMMVI_MAX_DIM_DIAG, route 1 with D above the cap, a NULL X / lp / handle, a handle of another context: GMMVI_ERR_ARG
+ * before any launch. */
+int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                        const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int route);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
@@ -421,8 +458,8 @@ int gmmvi_weight_stepsize_improvement(gmmvi_ctx* ctx, int K, const float* logw_d
 /* The built-in target of an iteration, described once for both plans below.  Only the members of `kind` are read. */
 typedef struct gmmvi_target_spec {
     int32_t kind;                         /* 0: mixture family (gmmvi_mixture_eval), 1: planar robot, 2: logistic regression,
-                                           * 4: Talos (gmmvi_target_talos); any other value, 3 included (no target has it):
-                                           * GMMVI_ERR_ARG */
+                                           * 4: Talos (gmmvi_target_talos), 5: user-defined (gmmvi_target_custom, route 0); any other
+                                           * value, 3 included (no target has it): GMMVI_ERR_ARG */
     /* kind 0 */
     int32_t mix_family, mix_K;            /* enum gmmvi_family, number of target components */
     float mix_nu;
@@ -440,6 +477,9 @@ typedef struct gmmvi_target_spec {
     /* kind 4 (gmmvi_target_talos, D == 34): the packed model table, the left gripper's goal [3] */
     const float* talos_model;
     const float* talos_context;
+    /* kind 5 (gmmvi_target_custom): the compiled target (NULL: GMMVI_ERR_ARG) and its params_dev (may be NULL) */
+    const gmmvi_custom_target* custom;
+    const float* custom_params;
 } gmmvi_target_spec;
 /* One stepsize rule (component_stepsize_adaptation.py:165-188, weight_stepsize_adaptation.py:141-156). */
 typedef struct gmmvi_stepsize_rule {
