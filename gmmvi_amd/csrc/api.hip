@@ -19,6 +19,16 @@ int gmmvi_ws_reserve(gmmvi_ctx* ctx, size_t nbytes) {
     return GMMVI_OK;
 }
 
+int gmmvi_ensure_dynamic_lds(gmmvi_ctx* ctx, const void* func, size_t bytes) {
+    size_t* set = nullptr;
+    for (auto& e : ctx->lds_limits)
+        if (e.first == func) { set = &e.second; break; }
+    if (bytes <= (set ? *set : (size_t)64 * 1024)) return GMMVI_OK;
+    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (set) *set = bytes; else ctx->lds_limits.emplace_back(func, bytes);
+    return GMMVI_OK;
+}
+
 extern "C" {
 
 int gmmvi_device_count(void) {

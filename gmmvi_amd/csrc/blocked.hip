@@ -1419,12 +1419,9 @@ static int blk_threads_mm(int D) { return D <= 320 ? 64 * ((D + 31) / 32) : blk_
 
 // the factorisation kernels stage up to ~70 KB of LDS at D = 512: raise the dynamic limit once
 static int blk_lds_attr(gmmvi_ctx* ctx) {
-    if (ctx->func_attr_done & 4u) return GMMVI_OK;          // per device: remembered per context
-    const int lim = 156 * 1024;            // (the kernels also hold a few static words)
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)blk_pack_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)blk_cholesky_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lim));
-    ctx->func_attr_done |= 4u;
-    return GMMVI_OK;
+    const size_t lim = 156 * 1024;         // (the kernels also hold a few static words)
+    BLK_TRY(gmmvi_ensure_dynamic_lds(ctx, (const void*)blk_pack_kernel, lim));
+    return gmmvi_ensure_dynamic_lds(ctx, (const void*)blk_cholesky_kernel, lim);
 }
 
 int gmmvi_blocked_pack(gmmvi_ctx* ctx, int family, float nu, int K, int D, const float* means, const float* chols,
@@ -2485,21 +2482,13 @@ int gmmvi_blocked_update_kl(gmmvi_ctx* ctx, int K, int D, float* means, float* c
     {
         const size_t lds_cols = ((size_t)3 * D + (size_t)2 * D * 64) * sizeof(float);
         const bool in_lds = lds_cols <= 156 * 1024;           // (the kernel's static LDS words need room beside it)
-        if (in_lds && !(ctx->func_attr_done & 1u)) {           // the attribute is per DEVICE: remembered per context
-            GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)blk_search_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                     156 * 1024));
-            ctx->func_attr_done |= 1u;
-        }
+        if (in_lds) BLK_TRY(gmmvi_ensure_dynamic_lds(ctx, (const void*)blk_search_kernel, 156 * 1024));
         hipLaunchKernelGGL(blk_search_kernel, dim3(K), dim3(64), in_lds ? lds_cols : (size_t)3 * D * sizeof(float), ctx->stream, D,
                            td, te, wt, stepsizes, last_eta, temperature, in_lds ? nullptr : scratch, state);
     }
     GMMVI_LAUNCH_CHECK(ctx);
     {
-        if (!(ctx->func_attr_done & 2u)) {                     // per device: remembered per context
-            GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)blk_upd_final_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-            ctx->func_attr_done |= 2u;
-        }
+        BLK_TRY(gmmvi_ensure_dynamic_lds(ctx, (const void*)blk_upd_final_kernel, 156 * 1024));
         const size_t a = blk_trsm_lds_floats(D), b = blk_chol_lds_floats(D);
         hipLaunchKernelGGL(blk_upd_final_kernel, dim3(K), dim3(blk_threads_mm(D + 1)), (a > b ? a : b) * sizeof(float), ctx->stream, D,
                            0, Mc, w, T1, Xs, state, means, chols, l2_init, last_eta, l2, num_updates, success_out, kl_out,
@@ -2555,11 +2544,7 @@ int gmmvi_blocked_update_plain(gmmvi_ctx* ctx, int mode, int K, int D, float* me
                        means, stepsizes, num_updates, Sig, T2, Qp, vec);
     GMMVI_LAUNCH_CHECK(ctx);
     {
-        if (!(ctx->func_attr_done & 2u)) {                     // per device: remembered per context
-            GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)blk_upd_final_kernel,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024));
-            ctx->func_attr_done |= 2u;
-        }
+        BLK_TRY(gmmvi_ensure_dynamic_lds(ctx, (const void*)blk_upd_final_kernel, 156 * 1024));
         const size_t a = blk_trsm_lds_floats(D), b = blk_chol_lds_floats(D);
         hipLaunchKernelGGL(blk_upd_final_kernel, dim3(K), dim3(blk_threads_mm(D + 1)), (a > b ? a : b) * sizeof(float), ctx->stream, D,
                            mode == 0 ? 1 : 2, Qp, vec, W, Xs, nullptr, means, chols, l2_init, nullptr, l2, num_updates,

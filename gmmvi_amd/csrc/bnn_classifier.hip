@@ -441,13 +441,9 @@ __global__ __launch_bounds__(BC_THREADS) void bnn_classifier_predict_kernel(int 
 namespace {
 bool bc_shape_ok(int F, int H, int C) { return F >= 1 && F <= BC_FMAX && H >= 1 && H <= BC_HP && C >= 2 && C <= BC_CP; }
 
-// the kernels' dynamic LDS lies above the 64 KB default: raise the limit once per context (the attribute is per device)
+// the kernel's dynamic LDS lies above the 64 KB default
 int bc_lds_attr(gmmvi_ctx* ctx) {
-    if (ctx->func_attr_done & 16u) return GMMVI_OK;
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)bnn_classifier_target_kernel,
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, BC_TARGET_FLOATS * (int)sizeof(float)));
-    ctx->func_attr_done |= 16u;
-    return GMMVI_OK;
+    return gmmvi_ensure_dynamic_lds(ctx, (const void*)bnn_classifier_target_kernel, BC_TARGET_FLOATS * sizeof(float));
 }
 }  // namespace
 

@@ -406,14 +406,11 @@ int ml_net(gmmvi_ctx* ctx, const gmmvi_mlp_desc* d, MlpNet* net) {
     return GMMVI_OK;
 }
 
-// the kernels' dynamic LDS lies above the 64 KB default: raise the limit once per context (the attribute is per device)
+// the kernels' dynamic LDS lies above the 64 KB default
 int ml_lds_attr(gmmvi_ctx* ctx) {
-    if (ctx->func_attr_done & 32u) return GMMVI_OK;
-    const int bytes = (int)ml_lds_bytes(GMMVI_MLP_MAX_LAYERS);
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)bnn_mlp_target_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)bnn_mlp_predict_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-    ctx->func_attr_done |= 32u;
-    return GMMVI_OK;
+    const size_t bytes = ml_lds_bytes(GMMVI_MLP_MAX_LAYERS);
+    const int rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)bnn_mlp_target_kernel, bytes);
+    return rc != GMMVI_OK ? rc : gmmvi_ensure_dynamic_lds(ctx, (const void*)bnn_mlp_predict_kernel, bytes);
 }
 }  // namespace
 

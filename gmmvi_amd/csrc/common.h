@@ -5,6 +5,7 @@
 #include <cstring>
 #include <cstdint>
 #include <string>
+#include <utility>
 #include <vector>
 #include "../../include/gmmvi_hip.h"
 #include "iter_prep.h"
@@ -71,7 +72,7 @@ struct gmmvi_ctx {
     std::vector<gmmvi_custom_target*> custom_targets;   // loaded user-defined targets (custom_target.hip), released with the context
     int n_ranks = 1, rank = 0;
     int num_cus = 256;
-    unsigned func_attr_done = 0; // bits: per-device kernel attributes (dynamic LDS above 64 KB) already set for this context's device
+    std::vector<std::pair<const void*, size_t>> lds_limits;   // (kernel, dynamic-LDS limit set on this context's device): gmmvi_ensure_dynamic_lds
     // optional per-kernel HIP-event timing (bench.py roofline leg): events are recorded on ctx->stream
     bool prof = false;
     const char* prof_tag = nullptr;   // set by a caller that knows which sweep of the iteration a density launch is (fused.hip)
@@ -119,6 +120,9 @@ inline int gmmvi_fail(gmmvi_ctx* ctx, int code, const std::string& msg) {
 #define GMMVI_LAUNCH_CHECK(ctx) GMMVI_HIP_CHECK(ctx, hipGetLastError())
 
 int gmmvi_ws_reserve(gmmvi_ctx* ctx, size_t nbytes);
+// api.hip: raises the dynamic-LDS limit of kernel `func` to `bytes` unless this context has already set as much (the attribute is
+// per device, so it is remembered per context); nothing to do up to the 64 KB every kernel may use
+int gmmvi_ensure_dynamic_lds(gmmvi_ctx* ctx, const void* func, size_t bytes);
 // custom_target.hip: unloads every user-defined target of the context (gmmvi_ctx_destroy)
 void gmmvi_custom_targets_destroy(gmmvi_ctx* ctx);
 // density.hip: component blocks in the register-path layout (Pack<padded D>, D <= 64) regardless of the blocked threshold
@@ -157,9 +161,7 @@ int gmmvi_update_components_kl_from_slab(gmmvi_ctx* ctx, int K, int D, const Ste
                                          int32_t* success_out_dev, float* packed_out_dev);
 // more_blocked.hip: the fp64 panel solver of the MORE ridge systems (mb_chol_* / mb_backsub kernels), shared with
 // more_diag.hip.  G[kg][LDG][LDG] holds the lower triangles, LDG a multiple of 128 with LDG >= F + 1, row F the right-hand
-// side; fail[kg] must be zeroed by the caller.  attrs: dynamic-LDS attributes of the four kernels (once per context);
-// ws_budget: the workspace budget of one component group (GMMVI_MORE_WS_GB, read per call)
-size_t gmmvi_more_ws_budget_bytes();
+// side; fail[kg] must be zeroed by the caller.  attrs: dynamic-LDS limits of the four kernels
 int gmmvi_more_panel_attrs(gmmvi_ctx* ctx);
 int gmmvi_more_panel_cholesky(gmmvi_ctx* ctx, const char* prof_name, int F, int LDG, int kg, int k0, const float* l2_dev,
                               double* G, int* fail);

@@ -6,7 +6,8 @@
 //     phi(z) = [ z_i z_j (i <= j, row-major upper triangle),  z,  1 ]          F = D(D+1)/2 + D + 1
 // i.e. it solves  (Phi^T W Phi + lambda I') beta = Phi^T W rew   (bias row of I' is zero), then un-whitens.
 //
-//   more_lse_kernel     per component: log sum_n exp(ld[o,n] - bg[n])  (self-normalised weights, :353-356)
+//   more_lse_kernel     per component: log sum_n exp(ld[o,n] - bg[n])  (self-normalised weights, :353-356; more_common.h, as
+//                       everything the three routes share: weight and reward of a sample, tile layout, feature order)
 //   more_gram_kernel    the (F+1)x(F+1) Gram matrix of the rows  sqrt(w_n) [phi(z_n); rew_n]  -- one fp64-MFMA SYRK per
 //                       component: A = Phi^T W Phi, b = Phi^T W rew and sum w rew^2 in one contraction.  Workgroup =
 //                       (component, sample chunk), 8 waves; per 64-sample tile every wave substitutes z (SGPR-fed L), the
@@ -29,16 +30,11 @@
 // Sizes: the (F+1)x(F+1) triangle is held by one 1024-thread workgroup (36 doubles per thread): F + 1 <= 256  <=>
 // D <= 21.  The ridge system is solved by Cholesky (the reference calls tf.linalg.solve = pivoted LU); a non-positive
 // pivot marks the component's estimate as NaN, which the component updaters treat as a rejected update.
-#include "common.h"
+#include "more_common.h"
 #include "subst.h"
 #include "blocked.h"
-#include "more_lse.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 namespace {
-
-constexpr int PHI_LD = 68;       // LDS row stride (words) of the feature image: 64 samples + 4 -> b128 reads conflict-free
 
 template <int DP>
 __device__ __forceinline__ void more_forward_subst(const float* __restrict__ P, const float (&x)[DP], float (&z)[DP]) {
@@ -52,8 +48,7 @@ __device__ __forceinline__ void more_forward_subst(const float* __restrict__ P, 
     }
 }
 
-// D[i][j] of v_mfma_f64_16x16x4_f64 on gfx950: lane l, register r  ->  i = 4 r + l / 16, j = l % 16 (probed on the
-// hardware: tools/probe/mfma_f64_layout.hip); operands A[i = l % 16][k = l / 16], B[k = l / 16][j = l % 16].
+// (MFMA operand and result layout: more_common.h)
 template <int DP, int PP>
 __global__ __launch_bounds__(512) void more_gram_kernel(int D, int N, int tiles_per_chunk, int nb,
                                                         const float* __restrict__ packed, const float* __restrict__ X,
@@ -70,10 +65,8 @@ __global__ __launch_bounds__(512) void more_gram_kernel(int D, int N, int tiles_
     const int T2 = D * (D + 1) / 2;                    // quadratic features
     const int F = T2 + D + 1;                          // features; row F carries the reward
     const int n_pairs = nb * (nb + 1) / 2;
-    const bool own_only = (flags & GMMVI_OWN_SAMPLES_ONLY) != 0;
-    const bool self_norm = (flags & GMMVI_SELF_NORMALIZED) != 0;
     const float* __restrict__ P = packed + (size_t)k * PK::STRIDE;
-    const float lse_k = self_norm ? lse[k] : 0.f;
+    const float lse_k = (flags & GMMVI_SELF_NORMALIZED) ? lse[k] : 0.f;
     const int ZS_TILE = (D + 3) * 64;                  // per tile: rows 0..D-1 z, row D ones, D+1 reward, D+2 sqrt(weight)
     float* zs = phi + 16 * nb * PHI_LD;                // 8 tiles, whitened one per wave
     int* tab = reinterpret_cast<int*>(zs + 8 * ZS_TILE);   // feature f -> (row ia) | (row ib) << 16 of a zs tile
@@ -95,17 +88,7 @@ __global__ __launch_bounds__(512) void more_gram_kernel(int D, int N, int tiles_
     for (int pp = 0; pp < PP; ++pp) acc[pp] = f64x4{0.0, 0.0, 0.0, 0.0};
 
     for (int e = tid; e < 16 * nb * PHI_LD; e += 512) phi[e] = 0.f;       // rows > F stay zero for the whole kernel
-    for (int f = tid; f <= F; f += 512) {                                 // least_squares.py:113-124 feature order
-        int ia, ib;
-        if (f < T2) {
-            int i = 0, rem = f;
-            while (rem >= D - i) { rem -= D - i; ++i; }
-            ia = i; ib = i + rem;
-        } else if (f < T2 + D) { ia = f - T2; ib = D; }
-        else if (f == F - 1) { ia = D; ib = D; }
-        else { ia = D + 1; ib = D; }
-        tab[f] = ia | (ib << 16);
-    }
+    for (int f = tid; f <= F; f += 512) tab[f] = more_feature_code(f, D);
     __syncthreads();
 
     const int r16 = lane & 15, kg = lane >> 4;
@@ -121,21 +104,13 @@ __global__ __launch_bounds__(512) void more_gram_kernel(int D, int N, int tiles_
 #pragma unroll
             for (int i = 0; i < DP; ++i) x[i] = (valid && i < D) ? X[(size_t)n * D + i] : P[PK::MU + i];
             more_forward_subst<DP>(P, x, z);
-            float sw = 0.f, rew = 0.f;
-            if (valid) {
-                float a;
-                if (own_only) a = (mapping[n] + map_offset == k) ? 0.f : -3.0e38f;
-                else a = ld[(size_t)k * N + n] - bg[n];
-                if (a > -3.0e38f) sw = __expf(0.5f * (a - lse_k));       // sqrt of the importance weight (:353-358)
-                rew = tlp[n] - logq[n];                                  // ng_estimator.py:346
-            }
+            float sw, rew;
+            more_weight_reward(k, n, N, ld, bg, tlp, logq, mapping, map_offset, flags, lse_k, sw, rew);
             const bool live = sw > 0.f;
 #pragma unroll
             for (int i = 0; i < DP; ++i)
                 if (i < D) zw[i * 64 + lane] = live ? z[i] : 0.f;
-            zw[D * 64 + lane] = 1.f;
-            zw[(D + 1) * 64 + lane] = live ? rew : 0.f;
-            zw[(D + 2) * 64 + lane] = live ? sw : 0.f;
+            more_write_trailer(zw, D, lane, sw, rew);
         }
         __syncthreads();
       for (int u = 0; u < 8 && t0 + u < tile_end; ++u) {
@@ -411,35 +386,19 @@ __global__ __launch_bounds__(512) void more_gram_big_kernel(int D, int N, int nb
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = blockIdx.y;
-    int BI = 0;
-    while ((BI + 1) * (BI + 2) / 2 <= (int)blockIdx.x) ++BI;
-    const int BC = (int)blockIdx.x - BI * (BI + 1) / 2;
+    int BI, BC;
+    more_block_of(blockIdx.x, BI, BC);
     const bool diag = BI == BC;
-    const int T2 = D * (D + 1) / 2;
-    const int F = T2 + D + 1;                          // features; row F carries the reward
-    const bool own_only = (flags & GMMVI_OWN_SAMPLES_ONLY) != 0;
-    const bool self_norm = (flags & GMMVI_SELF_NORMALIZED) != 0;
+    const int F = D * (D + 1) / 2 + D + 1;             // features; row F carries the reward
     const float* __restrict__ P = packed + (size_t)k * PK::STRIDE;
-    const float lse_k = self_norm ? lse[k] : 0.f;
+    const float lse_k = (flags & GMMVI_SELF_NORMALIZED) ? lse[k] : 0.f;
     const int ZS_TILE = (D + 3) * 64;                  // per tile: rows 0..D-1 z, row D ones, D+1 reward, D+2 sqrt(weight)
     float* zs = phi + 256 * PHI_LD;                    // 4 tiles
     int* tab = reinterpret_cast<int*>(zs + 4 * ZS_TILE);   // local row (0..255) -> (row ia) | (row ib) << 16 of a zs tile, or -1
     const int n_rows = diag ? 128 : 256;
     for (int r = tid; r < 256; r += 512) {
         const int f = 128 * (r < 128 ? BI : BC) + (r & 127);
-        int code = -1;
-        if (r < n_rows && f <= F) {                                     // least_squares.py:113-124 feature order
-            int ia, ib;
-            if (f < T2) {
-                int i = 0, rem = f;
-                while (rem >= D - i) { rem -= D - i; ++i; }
-                ia = i; ib = i + rem;
-            } else if (f < T2 + D) { ia = f - T2; ib = D; }
-            else if (f == F - 1) { ia = D; ib = D; }
-            else { ia = D + 1; ib = D; }
-            code = ia | (ib << 16);
-        }
-        tab[r] = code;
+        tab[r] = (r < n_rows && f <= F) ? more_feature_code(f, D) : -1;
     }
     for (int e = tid; e < 256 * PHI_LD; e += 512) phi[e] = 0.f;         // rows without a feature stay zero
     __syncthreads();
@@ -460,21 +419,13 @@ __global__ __launch_bounds__(512) void more_gram_big_kernel(int D, int N, int nb
 #pragma unroll
             for (int i = 0; i < DP; ++i) x[i] = (valid && i < D) ? X[(size_t)n * D + i] : P[PK::MU + i];
             more_forward_subst<DP>(P, x, z);
-            float sw = 0.f, rew = 0.f;
-            if (valid) {
-                float a;
-                if (own_only) a = (mapping[n] + map_offset == k) ? 0.f : -3.0e38f;
-                else a = ld[(size_t)k * N + n] - bg[n];
-                if (a > -3.0e38f) sw = __expf(0.5f * (a - lse_k));       // sqrt of the importance weight (:353-358)
-                rew = tlp[n] - logq[n];                                  // ng_estimator.py:346
-            }
+            float sw, rew;
+            more_weight_reward(k, n, N, ld, bg, tlp, logq, mapping, map_offset, flags, lse_k, sw, rew);
             const bool live = sw > 0.f;
 #pragma unroll
             for (int i = 0; i < DP; ++i)
                 if (i < D) zw[i * 64 + lane] = live ? z[i] : 0.f;
-            zw[D * 64 + lane] = 1.f;
-            zw[(D + 1) * 64 + lane] = live ? rew : 0.f;
-            zw[(D + 2) * 64 + lane] = live ? sw : 0.f;
+            more_write_trailer(zw, D, lane, sw, rew);
         }
         __syncthreads();
         for (int u = 0; u < 4 && t0 + u < n_tiles; ++u) {
@@ -488,41 +439,11 @@ __global__ __launch_bounds__(512) void more_gram_big_kernel(int D, int N, int nb
                 }
             }
             __syncthreads();
-#pragma unroll
-            for (int pp = 0; pp < 8; ++pp) {
-                const int q = wave + 8 * pp;
-                const float* pa = phi + (16 * (q >> 3) + r16) * PHI_LD + 4 * kg;
-                const float* pb = phi + (col_base + 16 * (q & 7) + r16) * PHI_LD + 4 * kg;
-                float4 av[4], bv[4];
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    av[qq] = *reinterpret_cast<const float4*>(pa + 16 * qq);
-                    bv[qq] = *reinterpret_cast<const float4*>(pb + 16 * qq);
-                }
-#pragma unroll
-                for (int qq = 0; qq < 4; ++qq) {
-                    acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].x, (double)bv[qq].x, acc[pp], 0, 0, 0);
-                    acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].y, (double)bv[qq].y, acc[pp], 0, 0, 0);
-                    acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].z, (double)bv[qq].z, acc[pp], 0, 0, 0);
-                    acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].w, (double)bv[qq].w, acc[pp], 0, 0, 0);
-                }
-            }
+            more_contract_block(phi, wave, r16, kg, col_base, acc);
             __syncthreads();
         }
     }
-    // D[i][j] of the fp64 MFMA: lane l, register r -> i = 4 r + l / 16, j = l % 16
-    double* Gk = G + (size_t)k * LDG * LDG;
-#pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-        const int q = wave + 8 * pp;
-        const int ti = q >> 3, tj = q & 7;
-        if (diag && tj > ti) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gi = 128 * BI + 16 * ti + 4 * r + kg, gj = 128 * BC + 16 * tj + r16;
-            Gk[(size_t)gi * LDG + gj] = acc[pp][r];
-        }
-    }
+    more_store_block(G + (size_t)k * LDG * LDG, LDG, BI, BC, wave, r16, kg, acc);
 }
 
 // One workgroup per component; see the banner above.  G: [LDG][LDG] fp64, lower triangle + row F valid on entry.
@@ -727,18 +648,11 @@ int launch_more_big(gmmvi_ctx* ctx, int K, int D, const float* packed, const flo
     double* G = (double*)ctx->ws;
     double* beta = G + g_doubles;
     float* lse = (float*)(beta + b_doubles);
-    if (flags & GMMVI_SELF_NORMALIZED) {
-        GMMVI_PROF(ctx, "more_lse");
-        hipLaunchKernelGGL(more_lse_kernel, dim3(K), dim3(1024), 0, ctx->stream, N, ld, bg, mapping, map_offset, flags, lse);
-        GMMVI_LAUNCH_CHECK(ctx);
-    }
+    rc = more_launch_lse(ctx, "more_lse", K, N, ld, bg, mapping, map_offset, flags, lse);
+    if (rc != GMMVI_OK) return rc;
     const size_t gram_lds = ((size_t)256 * PHI_LD + (size_t)4 * (D + 3) * 64 + 256) * sizeof(float);
-    static size_t gram_attr = 0;
-    if (gram_lds > gram_attr) {
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)more_gram_big_kernel<DP>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
-        gram_attr = gram_lds;
-    }
+    rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)more_gram_big_kernel<DP>, gram_lds);
+    if (rc != GMMVI_OK) return rc;
     {
         GMMVI_PROF(ctx, "more_gram");
         hipLaunchKernelGGL((more_gram_big_kernel<DP>), dim3(nblk * (nblk + 1) / 2, K), dim3(512), gram_lds, ctx->stream, D, N,
@@ -749,12 +663,8 @@ int launch_more_big(gmmvi_ctx* ctx, int K, int D, const float* packed, const flo
     const size_t unwhiten = (size_t)D * D + 2 * (size_t)D * (D + 1);
     if (unwhiten > solve_doubles) solve_doubles = unwhiten;
     const size_t solve_lds = solve_doubles * sizeof(double);
-    static size_t solve_attr = 0;
-    if (solve_lds > solve_attr) {
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)more_solve_big_kernel,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds));
-        solve_attr = solve_lds;
-    }
+    rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)more_solve_big_kernel, solve_lds);
+    if (rc != GMMVI_OK) return rc;
     GMMVI_PROF(ctx, "more_solve");
     hipLaunchKernelGGL(more_solve_big_kernel, dim3(K), dim3(1024), solve_lds, ctx->stream, D, LDG, G, chols, l2, H_neg, g_neg,
                        beta);
@@ -792,18 +702,11 @@ int launch_more(gmmvi_ctx* ctx, int K, int D, const float* packed, const float* 
     if (rc != GMMVI_OK) return rc;
     double* slab = (double*)ctx->ws;
     float* lse = (float*)(slab + slab_doubles);
-    if (flags & GMMVI_SELF_NORMALIZED) {
-        GMMVI_PROF(ctx, "more_lse");
-        hipLaunchKernelGGL(more_lse_kernel, dim3(K), dim3(1024), 0, ctx->stream, N, ld, bg, mapping, map_offset, flags, lse);
-        GMMVI_LAUNCH_CHECK(ctx);
-    }
+    rc = more_launch_lse(ctx, "more_lse", K, N, ld, bg, mapping, map_offset, flags, lse);
+    if (rc != GMMVI_OK) return rc;
     const size_t gram_lds = ((size_t)16 * nb * PHI_LD + (size_t)8 * (D + 3) * 64 + (size_t)(F + 1)) * sizeof(float);
-    static size_t gram_attr = 0;
-    if (gram_lds > gram_attr) {
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)more_gram_kernel<DP, PP>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)gram_lds));
-        gram_attr = gram_lds;
-    }
+    rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)more_gram_kernel<DP, PP>, gram_lds);
+    if (rc != GMMVI_OK) return rc;
     {
         GMMVI_PROF(ctx, "more_gram");
         hipLaunchKernelGGL((more_gram_kernel<DP, PP>), dim3(n_chunks, K), dim3(512), gram_lds, ctx->stream, D, N,

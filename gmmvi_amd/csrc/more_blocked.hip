@@ -1,9 +1,7 @@
 // MORE natural-gradient estimate for the blocked-path dimensions 64 <= D <= 128 (gmmvi_more_blocked), gfx950.
 //
-// Same mathematics as more.hip (its banner is the specification): features phi(z) = [z_i z_j (i <= j), z, 1] of the whitened
-// samples z = L^-1 (x - mu), the Gram matrix of the rows sqrt(w_n) [phi(z_n); rew_n] accumulated in fp64 from fp32 rows, the
-// ridge on all rows but the bias, fp64 Cholesky with the right-hand side riding along as row F, back substitution,
-// un-whitening.  F + 1 = 2 146 (D = 64) ... 8 386 (D = 128).  What differs from more_gram_big / more_solve_big:
+// Same mathematics as more.hip (its banner is the specification; the shared pieces, the workspace plan and the group loop are
+// in more_common.h).  F + 1 = 2 146 (D = 64) ... 8 386 (D = 128).  What differs from more_gram_big / more_solve_big:
 //
 //   mb_whiten_kernel   workgroup = (64-sample tile, component).  z comes from the dense L^-1 of the blocked component block
 //                      [mu | log-normaliser | pad | L^-1]: the tile of x - mu sits in LDS, wave w computes the rows w, w + 4, ...
@@ -30,27 +28,17 @@
 //   mb_unwhiten_*      H = L^-T Q_w L^-1, g = -L^-T lin_w with the SAME dense fp32 L^-1 that whitened the samples (a reward
 //                      that is quadratic in x is then recovered whatever the rounding of L^-1); chols_dev is not read
 //
-// Workspace: G is LDG^2 doubles per component (LDG = 128 ceil((F + 1) / 128): 563 MB at D = 128).  The components are
-// processed in groups whose request stays under a budget (default 8 GiB, GMMVI_MORE_WS_GB, read per call; at least one
-// component per group).  Every component is computed by the same launches whatever its group, so the results do not depend
-// on the group size.
-//
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; no scratch, no spills in any kernel):
-//   mb_gram_kernel 162 VGPR, 0 AGPR, 104 KB LDS at D = 128 (one 512-thread workgroup per CU); mb_chol_update_kernel 96 VGPR,
+//   mb_gram_kernel 172 VGPR, 0 AGPR, 104 KB LDS at D = 128 (one 512-thread workgroup per CU); mb_chol_update_kernel 96 VGPR,
 //   0 AGPR, 68 KB LDS (two workgroups per CU); mb_chol_diag / _panel / mb_backsub / mb_whiten 26 / 64 / 40 / 16 VGPR.
 // Measured deviations and times: DESIGN.md section 4.
 // The Cholesky and back-substitution launches are also reachable as gmmvi_more_panel_* (common.h): more_diag.hip solves its
 // F = 2 D + 1 systems with them.
-#include "common.h"
+#include "more_common.h"
 #include "blocked.h"
-#include "more_lse.h"
-
-typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-constexpr int PHI_LD = 68;       // LDS row stride (words) of the feature image: 64 samples + 4 -> b128 reads conflict-free
-constexpr int TB = 128;          // tile edge of G = panel width of the factorisation
 constexpr int A_LD = TB + 1;     // LDS row stride (doubles) of a block whose rows belong to consecutive lanes
 constexpr int UP_KC = 32;        // columns of the panel staged per step of the trailing update
 constexpr int UP_LD = UP_KC + 2; // LDS row stride (doubles): 16 rows x 2 k-groups of a half-wave fall on 32 distinct bank pairs
@@ -74,15 +62,9 @@ __global__ __launch_bounds__(256) void mb_whiten_kernel(int D, int N, int n_tile
         xs[j * 65 + s] = (n0 + s < N) ? X[(size_t)(n0 + s) * D + j] - P[j] : 0.f;
     }
     const int n = n0 + lane;
-    float sw = 0.f, rew = 0.f;
-    if (n < N) {
-        float a;
-        if (flags & GMMVI_OWN_SAMPLES_ONLY) a = (mapping[n] + map_offset == k) ? 0.f : -3.0e38f;
-        else a = ld[(size_t)k * N + n] - bg[n];
-        const float lse_k = (flags & GMMVI_SELF_NORMALIZED) ? lse[k] : 0.f;
-        if (a > -3.0e38f) sw = __expf(0.5f * (a - lse_k));               // sqrt of the importance weight (:353-358)
-        rew = tlp[n] - logq[n];                                          // ng_estimator.py:346
-    }
+    float sw, rew;
+    more_weight_reward(k, n, N, ld, bg, tlp, logq, mapping, map_offset, flags, (flags & GMMVI_SELF_NORMALIZED) ? lse[k] : 0.f,
+                       sw, rew);
     const bool live = sw > 0.f;
     __syncthreads();
     float* __restrict__ out = Zt + ((size_t)kk * n_tiles + tile) * (size_t)(D + 3) * 64;
@@ -92,15 +74,10 @@ __global__ __launch_bounds__(256) void mb_whiten_kernel(int D, int N, int n_tile
         for (int j = 0; j <= i; ++j) t = fmaf(row[j], xs[j * 65 + lane], t);
         out[i * 64 + lane] = live ? t : 0.f;
     }
-    if (wave == 0) {
-        out[D * 64 + lane] = 1.f;
-        out[(D + 1) * 64 + lane] = live ? rew : 0.f;
-        out[(D + 2) * 64 + lane] = live ? sw : 0.f;
-    }
+    if (wave == 0) more_write_trailer(out, D, lane, sw, rew);
 }
 
-// D[i][j] of v_mfma_f64_16x16x4_f64 on gfx950: lane l, register r  ->  i = 4 r + l / 16, j = l % 16; operands
-// A[i = l % 16][k = l / 16], B[k = l / 16][j = l % 16] (more.hip).
+// (MFMA operand and result layout: more_common.h)
 __global__ __launch_bounds__(512) void mb_gram_kernel(int D, int n_tiles, int LDG, const float* __restrict__ Zt,
                                                       double* __restrict__ G) {
     extern __shared__ float phi[];                     // [256][PHI_LD] feature rows of the two blocks, one staged tile, tab
@@ -108,31 +85,17 @@ __global__ __launch_bounds__(512) void mb_gram_kernel(int D, int n_tiles, int LD
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = blockIdx.y;
-    int BI = 0;
-    while ((BI + 1) * (BI + 2) / 2 <= (int)blockIdx.x) ++BI;
-    const int BC = (int)blockIdx.x - BI * (BI + 1) / 2;
+    int BI, BC;
+    more_block_of(blockIdx.x, BI, BC);
     const bool diag = BI == BC;
-    const int T2 = D * (D + 1) / 2;
-    const int F = T2 + D + 1;                          // features; row F carries the reward
+    const int F = D * (D + 1) / 2 + D + 1;             // features; row F carries the reward
     const int ZS = (D + 3) * 64;                       // per tile: rows 0..D-1 z, row D ones, D+1 reward, D+2 sqrt(weight)
     float* zs = phi + 256 * PHI_LD;
     int* tab = reinterpret_cast<int*>(zs + ZS);        // local row (0..255) -> (row ia) | (row ib) << 16 of the tile, or -1
     const int n_rows = diag ? 128 : 256;
     for (int r = tid; r < 256; r += 512) {
         const int f = TB * (r < 128 ? BI : BC) + (r & 127);
-        int code = -1;
-        if (r < n_rows && f <= F) {                                     // least_squares.py:113-124 feature order
-            int ia, ib;
-            if (f < T2) {
-                int i = 0, rem = f;
-                while (rem >= D - i) { rem -= D - i; ++i; }
-                ia = i; ib = i + rem;
-            } else if (f < T2 + D) { ia = f - T2; ib = D; }
-            else if (f == F - 1) { ia = D; ib = D; }
-            else { ia = D + 1; ib = D; }
-            code = ia | (ib << 16);
-        }
-        tab[r] = code;
+        tab[r] = (r < n_rows && f <= F) ? more_feature_code(f, D) : -1;
     }
     for (int e = tid; e < 256 * PHI_LD; e += 512) phi[e] = 0.f;         // rows without a feature stay zero
     const float* __restrict__ zsrc = Zt + (size_t)k * n_tiles * ZS;
@@ -163,25 +126,7 @@ __global__ __launch_bounds__(512) void mb_gram_kernel(int D, int n_tiles, int LD
             const int e = 4 * (tid + 512 * q);
             pre[q] = (more && e < ZS) ? *reinterpret_cast<const float4*>(znext + e) : float4{0.f, 0.f, 0.f, 0.f};
         }
-#pragma unroll
-        for (int pp = 0; pp < 8; ++pp) {
-            const int q = wave + 8 * pp;
-            const float* pa = phi + (16 * (q >> 3) + r16) * PHI_LD + 4 * kg;
-            const float* pb = phi + (col_base + 16 * (q & 7) + r16) * PHI_LD + 4 * kg;
-            float4 av[4], bv[4];
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                av[qq] = *reinterpret_cast<const float4*>(pa + 16 * qq);
-                bv[qq] = *reinterpret_cast<const float4*>(pb + 16 * qq);
-            }
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].x, (double)bv[qq].x, acc[pp], 0, 0, 0);
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].y, (double)bv[qq].y, acc[pp], 0, 0, 0);
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].z, (double)bv[qq].z, acc[pp], 0, 0, 0);
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].w, (double)bv[qq].w, acc[pp], 0, 0, 0);
-            }
-        }
+        more_contract_block(phi, wave, r16, kg, col_base, acc);
         if (more) {
 #pragma unroll
             for (int q = 0; q < Z_PRE; ++q) {
@@ -191,18 +136,7 @@ __global__ __launch_bounds__(512) void mb_gram_kernel(int D, int n_tiles, int LD
         }
         __syncthreads();
     }
-    double* Gk = G + (size_t)k * LDG * LDG;
-#pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-        const int q = wave + 8 * pp;
-        const int ti = q >> 3, tj = q & 7;
-        if (diag && tj > ti) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gi = TB * BI + 16 * ti + 4 * r + kg, gj = TB * BC + 16 * tj + r16;
-            Gk[(size_t)gi * LDG + gj] = acc[pp][r];
-        }
-    }
+    more_store_block(G + (size_t)k * LDG * LDG, LDG, BI, BC, wave, r16, kg, acc);
 }
 
 // Diagonal block of the panel at column jb: right-looking Cholesky in LDS, one barrier per column.  Column j stays
@@ -445,32 +379,19 @@ __global__ __launch_bounds__(128) void mb_unwhiten_left_kernel(int D, int LDG, i
     }
 }
 
-size_t more_ws_budget_bytes() {
-    // workspace budget of one component group (default 8 GiB); read per call so a test can shrink it
-    const char* e = getenv("GMMVI_MORE_WS_GB");
-    double gb = e ? atof(e) : 8.0;
-    if (!(gb > 0.0)) gb = 8.0;
-    return (size_t)(gb * (double)((size_t)1 << 30));
-}
-
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 // ---- the panel solver as internal entry points (common.h): gmmvi_more_blocked below and more_diag.hip launch the same kernels ----
-size_t gmmvi_more_ws_budget_bytes() { return more_ws_budget_bytes(); }
-
 int gmmvi_more_panel_attrs(gmmvi_ctx* ctx) {
-    if (ctx->func_attr_done & 64u) return GMMVI_OK;          // per device: remembered per context
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_diag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(((size_t)TB * A_LD + TB) * sizeof(double))));
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_panel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(((size_t)64 * A_LD + (size_t)TB * (TB + 1) / 2) * sizeof(double))));
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_chol_update_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)((size_t)2 * TB * UP_LD * sizeof(double))));
-    GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_backsub_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                             (int)(((size_t)TB * 66 + 2 * 32 * 33) * sizeof(double))));
-    ctx->func_attr_done |= 64u;
+    const struct { const void* func; size_t bytes; } limits[] = {
+        {(const void*)mb_chol_diag_kernel, ((size_t)TB * A_LD + TB) * sizeof(double)},
+        {(const void*)mb_chol_panel_kernel, ((size_t)64 * A_LD + (size_t)TB * (TB + 1) / 2) * sizeof(double)},
+        {(const void*)mb_chol_update_kernel, (size_t)2 * TB * UP_LD * sizeof(double)},
+        {(const void*)mb_backsub_kernel, ((size_t)TB * 66 + 2 * 32 * 33) * sizeof(double)}};
+    for (const auto& l : limits) {
+        const int rc = gmmvi_ensure_dynamic_lds(ctx, l.func, l.bytes);
+        if (rc != GMMVI_OK) return rc;
+    }
     return GMMVI_OK;
 }
 
@@ -525,78 +446,33 @@ extern "C" int gmmvi_more_blocked(gmmvi_ctx* ctx, int K, int D, const float* pac
         (own_only ? mapping_dev == nullptr : !(ld_dev && bg_dev)))
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "gmmvi_more_blocked: a required device pointer is null (64 <= D <= 128)");
 
-    const int F = D * (D + 1) / 2 + D + 1;
-    const int nblk = (F + 1 + TB - 1) / TB;
-    const int LDG = TB * nblk;
-    const int n_tiles = (N + 63) / 64;
     const size_t pstride = gmmvi_blocked_stride(D);
     const int linv_ofs = gmmvi_blocked_linv_ofs(D);
-
-    // workspace of a group of kg components: G | staged tiles | beta | T | fail flags, then the K log-normalisers
-    const size_t g_bytes = (size_t)LDG * LDG * sizeof(double);
-    const size_t z_bytes = align256((size_t)n_tiles * (D + 3) * 64 * sizeof(float));
-    const size_t b_bytes = align256((size_t)LDG * sizeof(double));
-    const size_t t_bytes = align256((size_t)D * D * sizeof(double));
-    const size_t per_comp = g_bytes + z_bytes + b_bytes + t_bytes;
-    const size_t fixed = align256((size_t)K * sizeof(int)) + align256((size_t)K * sizeof(float));
-    const size_t budget = more_ws_budget_bytes();
-    size_t kg_max = budget > fixed ? (budget - fixed) / per_comp : 0;
-    if (kg_max < 1) kg_max = 1;
-    const int KG = (int)(kg_max < (size_t)K ? kg_max : (size_t)K);
-    int rc = gmmvi_ws_reserve(ctx, (size_t)KG * per_comp + fixed);
+    static const MorePanelNames prof = {"more_blocked_lse", "more_blocked_whiten", "more_blocked_gram", "more_blocked_cholesky",
+                                        "more_blocked_solve"};
+    MorePanelPlan p;
+    int rc = more_panel_plan(ctx, K, N, D, D * (D + 1) / 2 + D + 1, (size_t)D * D * sizeof(double), &p);
     if (rc != GMMVI_OK) return rc;
-    char* base = (char*)ctx->ws;
-    double* G = (double*)base;
-    float* Zt = (float*)(base + (size_t)KG * g_bytes);
-    double* beta = (double*)((char*)Zt + (size_t)KG * z_bytes);
-    double* T = (double*)((char*)beta + (size_t)KG * b_bytes);
-    int* fail = (int*)((char*)T + (size_t)KG * t_bytes);
-    float* lse = (float*)((char*)fail + align256((size_t)K * sizeof(int)));
-
     const size_t whiten_lds = (size_t)D * 65 * sizeof(float);
     const size_t gram_lds = ((size_t)256 * PHI_LD + (size_t)(D + 3) * 64 + 256) * sizeof(float);
-    if (!(ctx->func_attr_done & 8u)) {
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)mb_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)(((size_t)256 * PHI_LD + (size_t)(128 + 3) * 64 + 256) * sizeof(float))));
-        ctx->func_attr_done |= 8u;
-    }
-    rc = gmmvi_more_panel_attrs(ctx);
+    rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)mb_gram_kernel,                    // once: the limit of D = 128
+                                  ((size_t)256 * PHI_LD + (size_t)(128 + 3) * 64 + 256) * sizeof(float));
     if (rc != GMMVI_OK) return rc;
-
-    if (flags & GMMVI_SELF_NORMALIZED) {
-        GMMVI_PROF(ctx, "more_blocked_lse");
-        hipLaunchKernelGGL(more_lse_kernel, dim3(K), dim3(1024), 0, ctx->stream, N, ld_dev, bg_dev, mapping_dev, map_offset,
-                           flags, lse);
-        GMMVI_LAUNCH_CHECK(ctx);
-    }
-    for (int k0 = 0; k0 < K; k0 += KG) {
-        const int kg = K - k0 < KG ? K - k0 : KG;
-        GMMVI_HIP_CHECK(ctx, hipMemsetAsync(fail, 0, (size_t)kg * sizeof(int), ctx->stream));
-        {
-            GMMVI_PROF(ctx, "more_blocked_whiten");
-            hipLaunchKernelGGL(mb_whiten_kernel, dim3(n_tiles, kg), dim3(256), whiten_lds, ctx->stream, D, N, n_tiles, k0,
+    return more_panel_run(
+        ctx, p, prof, K, N, ld_dev, bg_dev, mapping_dev, map_offset, flags, l2_dev,
+        [&](int k0, int kg) {
+            hipLaunchKernelGGL(mb_whiten_kernel, dim3(p.n_tiles, kg), dim3(256), whiten_lds, ctx->stream, D, N, p.n_tiles, k0,
                                pstride, linv_ofs, packed_dev, X_dev, ld_dev, bg_dev, tlp_dev, logq_dev, mapping_dev, map_offset,
-                               flags, lse, Zt);
-            GMMVI_LAUNCH_CHECK(ctx);
-        }
-        {
-            GMMVI_PROF(ctx, "more_blocked_gram");
-            hipLaunchKernelGGL(mb_gram_kernel, dim3(nblk * (nblk + 1) / 2, kg), dim3(512), gram_lds, ctx->stream, D, n_tiles,
-                               LDG, Zt, G);
-            GMMVI_LAUNCH_CHECK(ctx);
-        }
-        rc = gmmvi_more_panel_cholesky(ctx, "more_blocked_cholesky", F, LDG, kg, k0, l2_dev, G, fail);
-        if (rc != GMMVI_OK) return rc;
-        {
-            GMMVI_PROF(ctx, "more_blocked_solve");
-            rc = gmmvi_more_panel_backsub(ctx, F, LDG, kg, G, fail, beta);
-            if (rc != GMMVI_OK) return rc;
-            hipLaunchKernelGGL(mb_unwhiten_right_kernel, dim3(D, kg), dim3(128), 0, ctx->stream, D, LDG, k0, pstride, linv_ofs,
-                               packed_dev, beta, fail, T);
-            hipLaunchKernelGGL(mb_unwhiten_left_kernel, dim3(D, kg), dim3(128), 0, ctx->stream, D, LDG, k0, pstride, linv_ofs,
-                               packed_dev, beta, fail, T, H_neg_out_dev, g_neg_out_dev);
-            GMMVI_LAUNCH_CHECK(ctx);
-        }
-    }
-    return GMMVI_OK;
+                               flags, p.lse, p.Zt);
+        },
+        [&](int kg) {
+            hipLaunchKernelGGL(mb_gram_kernel, dim3(p.nblk * (p.nblk + 1) / 2, kg), dim3(512), gram_lds, ctx->stream, D,
+                               p.n_tiles, p.LDG, p.Zt, p.G);
+        },
+        [&](int k0, int kg) {
+            hipLaunchKernelGGL(mb_unwhiten_right_kernel, dim3(D, kg), dim3(128), 0, ctx->stream, D, p.LDG, k0, pstride, linv_ofs,
+                               packed_dev, p.beta, p.fail, p.T);
+            hipLaunchKernelGGL(mb_unwhiten_left_kernel, dim3(D, kg), dim3(128), 0, ctx->stream, D, p.LDG, k0, pstride, linv_ofs,
+                               packed_dev, p.beta, p.fail, p.T, H_neg_out_dev, g_neg_out_dev);
+        });
 }

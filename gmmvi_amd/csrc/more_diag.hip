@@ -5,8 +5,8 @@
 // :126-191) restricted to a diagonal quadratic.  For component k with mean mu, standard deviations sigma (the diagonal
 // model's chol_cov[k]), ridge lambda = l2_regularizers[k], samples x_n, rewards r_n = target_lnpdfs[n] - log q(x_n)
 // (ng_estimator.py:347) and importance weights w_n:
-//   weights      exactly those of gmmvi_more (more.hip): GMMVI_SELF_NORMALIZED / GMMVI_OWN_SAMPLES_ONLY, mapping and map_offset
-//                keep their meaning, the double normalisation of SURVEY 2.2-7 is kept
+//   weights      exactly those of gmmvi_more (more_weight_reward, more_common.h): GMMVI_SELF_NORMALIZED / GMMVI_OWN_SAMPLES_ONLY,
+//                mapping and map_offset keep their meaning, the double normalisation of SURVEY 2.2-7 is kept
 //   whitening    z = (x - mu) / sigma, elementwise
 //   features     phi(z) = [z_1^2 .. z_D^2, z_1 .. z_D, 1]: the sufficient statistics of the component family, F = 2 D + 1
 //   regression   theta = (sum_n w_n phi_n phi_n^T + lambda I')^-1 sum_n w_n phi_n r_n, I' the identity with a zero at the bias
@@ -32,23 +32,15 @@
 //   md_unwhiten_kernel elementwise, with the SAME fp32 1 / sigma that whitened the samples (a reward that is a diagonal
 //                      quadratic in x is then recovered whatever the rounding of 1 / sigma).
 //
-// Workspace: G | staged tiles | theta | fail flags per component, the K log-normalisers behind them; components run in groups
-// under the budget of gmmvi_more_blocked (GMMVI_MORE_WS_GB, read per call, at least one component per group).  Every component
-// is computed by the same launches whatever its group: the results do not depend on the group size.
+// Workspace plan and group loop: those of gmmvi_more_blocked (more_common.h), without its T.
 // 1 <= D <= GMMVI_MORE_DIAG_MAX_DIM = 1024; above: GMMVI_ERR_ARG (larger D is out of scope: the dense F x F solve is the limit).
 //
 // Resources (hipcc -O3, gfx950, -Rpass-analysis=kernel-resource-usage; no scratch, no spills in any kernel):
-//   md_gram_kernel 216 VGPR, 0 AGPR, 68 KB LDS (one 512-thread workgroup per CU); md_stage_kernel 14 VGPR, 16.3 KB LDS; md_unwhiten_kernel 10 VGPR.
+//   md_gram_kernel 218 VGPR, 0 AGPR, 68 KB LDS (one 512-thread workgroup per CU); md_stage_kernel 14 VGPR, 16.3 KB LDS; md_unwhiten_kernel 10 VGPR.
 // Measured deviations: DESIGN.md section 4b.
-#include "common.h"
-#include "more_lse.h"
-
-typedef double md_f64x4 __attribute__((ext_vector_type(4)));
+#include "more_common.h"
 
 namespace {
-
-constexpr int PHI_LD = 68;       // LDS row stride (words) of the feature image: 64 samples + 4 -> b128 reads conflict-free
-constexpr int TB = 128;          // tile edge of G = panel width of the factorisation (more_blocked.hip)
 
 __global__ __launch_bounds__(256) void md_stage_kernel(int D, int N, int n_tiles, int k0, size_t pstride,
                                                        const float* __restrict__ packed, const float* __restrict__ X,
@@ -64,22 +56,12 @@ __global__ __launch_bounds__(256) void md_stage_kernel(int D, int N, int n_tiles
     const float* __restrict__ rsig = mu + D;
     const int n0 = tile * 64;
     const int n = n0 + lane;                           // every wave holds the weights of the tile's samples, lane = sample
-    float sw = 0.f, rew = 0.f;
-    if (n < N) {
-        float a;
-        if (flags & GMMVI_OWN_SAMPLES_ONLY) a = (mapping[n] + map_offset == k) ? 0.f : -3.0e38f;
-        else a = ld[(size_t)k * N + n] - bg[n];
-        const float lse_k = (flags & GMMVI_SELF_NORMALIZED) ? lse[k] : 0.f;
-        if (a > -3.0e38f) sw = __expf(0.5f * (a - lse_k));               // sqrt of the importance weight (:353-358)
-        rew = tlp[n] - logq[n];                                          // ng_estimator.py:347
-    }
+    float sw, rew;
+    more_weight_reward(k, n, N, ld, bg, tlp, logq, mapping, map_offset, flags, (flags & GMMVI_SELF_NORMALIZED) ? lse[k] : 0.f,
+                       sw, rew);
     const bool live = sw > 0.f;
     float* __restrict__ out = Zt + ((size_t)kk * n_tiles + tile) * (size_t)(D + 3) * 64;
-    if (wave == 0) {
-        out[D * 64 + lane] = 1.f;
-        out[(D + 1) * 64 + lane] = live ? rew : 0.f;
-        out[(D + 2) * 64 + lane] = live ? sw : 0.f;
-    }
+    if (wave == 0) more_write_trailer(out, D, lane, sw, rew);
     for (int c0 = 0; c0 < D; c0 += 64) {
         const int j = c0 + lane;                       // reading: lane = dimension (coalesced rows of X)
         const float m = j < D ? mu[j] : 0.f, r = j < D ? rsig[j] : 0.f;
@@ -92,8 +74,7 @@ __global__ __launch_bounds__(256) void md_stage_kernel(int D, int N, int n_tiles
     }
 }
 
-// D[i][j] of v_mfma_f64_16x16x4_f64 on gfx950: lane l, register r  ->  i = 4 r + l / 16, j = l % 16; operands
-// A[i = l % 16][k = l / 16], B[k = l / 16][j = l % 16] (more.hip).
+// (MFMA operand and result layout: more_common.h)
 // Row f of G: f < D z_f^2, f < 2 D z_{f - D}, f = 2 D the bias, f = F = 2 D + 1 the reward.
 __global__ __launch_bounds__(512) void md_gram_kernel(int D, int n_tiles, int LDG, const float* __restrict__ Zt,
                                                       double* __restrict__ G) {
@@ -102,9 +83,8 @@ __global__ __launch_bounds__(512) void md_gram_kernel(int D, int n_tiles, int LD
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int k = blockIdx.y;
-    int BI = 0;
-    while ((BI + 1) * (BI + 2) / 2 <= (int)blockIdx.x) ++BI;
-    const int BC = (int)blockIdx.x - BI * (BI + 1) / 2;
+    int BI, BC;
+    more_block_of(blockIdx.x, BI, BC);
     const bool diag = BI == BC;
     const int F = 2 * D + 1;
     const int ZS = (D + 3) * 64;                       // per tile: rows 0..D-1 z, row D ones, D+1 reward, D+2 sqrt(weight)
@@ -136,9 +116,9 @@ __global__ __launch_bounds__(512) void md_gram_kernel(int D, int n_tiles, int LD
     __syncthreads();
 
     // wave w owns the tile pairs p = w + 8 pp: row tile p / 8 of block BI, column tile p % 8 of block BC
-    md_f64x4 acc[8];
+    f64x4 acc[8];
 #pragma unroll
-    for (int pp = 0; pp < 8; ++pp) acc[pp] = md_f64x4{0.0, 0.0, 0.0, 0.0};
+    for (int pp = 0; pp < 8; ++pp) acc[pp] = f64x4{0.0, 0.0, 0.0, 0.0};
     const int r16 = lane & 15, kg = lane >> 4;
     const int col_base = diag ? 0 : 128;
     for (int t = 0; t < n_tiles; ++t) {
@@ -158,39 +138,10 @@ __global__ __launch_bounds__(512) void md_gram_kernel(int D, int n_tiles, int LD
             for (int q = 0; q < 8; ++q) pre[q] = src[q] >= 0 ? *reinterpret_cast<const float4*>(znext + src[q]) : zero4;
             psw = *reinterpret_cast<const float4*>(znext + (D + 2) * 64 + c4);
         }
-#pragma unroll
-        for (int pp = 0; pp < 8; ++pp) {
-            const int p = wave + 8 * pp;
-            const float* pa = phi + (16 * (p >> 3) + r16) * PHI_LD + 4 * kg;
-            const float* pb = phi + (col_base + 16 * (p & 7) + r16) * PHI_LD + 4 * kg;
-            float4 av[4], bv[4];
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                av[qq] = *reinterpret_cast<const float4*>(pa + 16 * qq);
-                bv[qq] = *reinterpret_cast<const float4*>(pb + 16 * qq);
-            }
-#pragma unroll
-            for (int qq = 0; qq < 4; ++qq) {
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].x, (double)bv[qq].x, acc[pp], 0, 0, 0);
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].y, (double)bv[qq].y, acc[pp], 0, 0, 0);
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].z, (double)bv[qq].z, acc[pp], 0, 0, 0);
-                acc[pp] = __builtin_amdgcn_mfma_f64_16x16x4f64((double)av[qq].w, (double)bv[qq].w, acc[pp], 0, 0, 0);
-            }
-        }
+        more_contract_block(phi, wave, r16, kg, col_base, acc);
         __syncthreads();
     }
-    double* Gk = G + (size_t)k * LDG * LDG;
-#pragma unroll
-    for (int pp = 0; pp < 8; ++pp) {
-        const int p = wave + 8 * pp;
-        const int ti = p >> 3, tj = p & 7;
-        if (diag && tj > ti) continue;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int gi = TB * BI + 16 * ti + 4 * r + kg, gj = TB * BC + 16 * tj + r16;
-            Gk[(size_t)gi * LDG + gj] = acc[pp][r];
-        }
-    }
+    more_store_block(G + (size_t)k * LDG * LDG, LDG, BI, BC, wave, r16, kg, acc);
 }
 
 // R_i = -2 theta_quad,i / sigma_i^2 (least_squares.py:177-185 on a diagonal), g_i = R_i mu_i - lin_i = -theta_lin,i / sigma_i
@@ -213,8 +164,6 @@ __global__ __launch_bounds__(256) void md_unwhiten_kernel(int D, int LDG, int k0
     g_neg[(size_t)k * D + i] = g;
 }
 
-size_t align256(size_t b) { return (b + 255) / 256 * 256; }
-
 }  // namespace
 
 extern "C" int gmmvi_more_diag(gmmvi_ctx* ctx, int K, int D, const float* packed_dev, const float* X_dev, int N,
@@ -233,71 +182,27 @@ extern "C" int gmmvi_more_diag(gmmvi_ctx* ctx, int K, int D, const float* packed
         (own_only ? mapping_dev == nullptr : !(ld_dev && bg_dev)))
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "gmmvi_more_diag: a required device pointer is null");
 
-    const int F = 2 * D + 1;
-    const int nblk = (F + 1 + TB - 1) / TB;
-    const int LDG = TB * nblk;
-    const int n_tiles = (N + 63) / 64;
     const size_t pstride = gmmvi_diag_packed_stride(D);
-
-    // workspace of a group of kg components: G | staged tiles | theta | fail flags, then the K log-normalisers
-    const size_t g_bytes = (size_t)LDG * LDG * sizeof(double);
-    const size_t z_bytes = align256((size_t)n_tiles * (D + 3) * 64 * sizeof(float));
-    const size_t b_bytes = align256((size_t)LDG * sizeof(double));
-    const size_t per_comp = g_bytes + z_bytes + b_bytes;
-    const size_t fixed = align256((size_t)K * sizeof(int)) + align256((size_t)K * sizeof(float));
-    const size_t budget = gmmvi_more_ws_budget_bytes();
-    size_t kg_max = budget > fixed ? (budget - fixed) / per_comp : 0;
-    if (kg_max < 1) kg_max = 1;
-    const int KG = (int)(kg_max < (size_t)K ? kg_max : (size_t)K);
-    int rc = gmmvi_ws_reserve(ctx, (size_t)KG * per_comp + fixed);
+    static const MorePanelNames prof = {"more_diag_lse", "more_diag_stage", "more_diag_gram", "more_diag_cholesky",
+                                        "more_diag_solve"};
+    MorePanelPlan p;
+    int rc = more_panel_plan(ctx, K, N, D, 2 * D + 1, 0, &p);
     if (rc != GMMVI_OK) return rc;
-    char* base = (char*)ctx->ws;
-    double* G = (double*)base;
-    float* Zt = (float*)(base + (size_t)KG * g_bytes);
-    double* beta = (double*)((char*)Zt + (size_t)KG * z_bytes);
-    int* fail = (int*)((char*)beta + (size_t)KG * b_bytes);
-    float* lse = (float*)((char*)fail + align256((size_t)K * sizeof(int)));
-
     const size_t gram_lds = (size_t)256 * PHI_LD * sizeof(float);
-    if (!(ctx->func_attr_done & 128u)) {
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)md_gram_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)gram_lds));
-        ctx->func_attr_done |= 128u;
-    }
-    rc = gmmvi_more_panel_attrs(ctx);
+    rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)md_gram_kernel, gram_lds);
     if (rc != GMMVI_OK) return rc;
-
-    if (flags & GMMVI_SELF_NORMALIZED) {
-        GMMVI_PROF(ctx, "more_diag_lse");
-        hipLaunchKernelGGL(more_lse_kernel, dim3(K), dim3(1024), 0, ctx->stream, N, ld_dev, bg_dev, mapping_dev, map_offset,
-                           flags, lse);
-        GMMVI_LAUNCH_CHECK(ctx);
-    }
-    for (int k0 = 0; k0 < K; k0 += KG) {
-        const int kg = K - k0 < KG ? K - k0 : KG;
-        GMMVI_HIP_CHECK(ctx, hipMemsetAsync(fail, 0, (size_t)kg * sizeof(int), ctx->stream));
-        {
-            GMMVI_PROF(ctx, "more_diag_stage");
-            hipLaunchKernelGGL(md_stage_kernel, dim3(n_tiles, kg), dim3(256), 0, ctx->stream, D, N, n_tiles, k0, pstride,
-                               packed_dev, X_dev, ld_dev, bg_dev, tlp_dev, logq_dev, mapping_dev, map_offset, flags, lse, Zt);
-            GMMVI_LAUNCH_CHECK(ctx);
-        }
-        {
-            GMMVI_PROF(ctx, "more_diag_gram");
-            hipLaunchKernelGGL(md_gram_kernel, dim3(nblk * (nblk + 1) / 2, kg), dim3(512), gram_lds, ctx->stream, D, n_tiles,
-                               LDG, Zt, G);
-            GMMVI_LAUNCH_CHECK(ctx);
-        }
-        rc = gmmvi_more_panel_cholesky(ctx, "more_diag_cholesky", F, LDG, kg, k0, l2_dev, G, fail);
-        if (rc != GMMVI_OK) return rc;
-        {
-            GMMVI_PROF(ctx, "more_diag_solve");
-            rc = gmmvi_more_panel_backsub(ctx, F, LDG, kg, G, fail, beta);
-            if (rc != GMMVI_OK) return rc;
-            hipLaunchKernelGGL(md_unwhiten_kernel, dim3((D + 255) / 256, kg), dim3(256), 0, ctx->stream, D, LDG, k0, pstride,
-                               packed_dev, beta, fail, h_neg_diag_out_dev, g_neg_out_dev);
-            GMMVI_LAUNCH_CHECK(ctx);
-        }
-    }
-    return GMMVI_OK;
+    return more_panel_run(
+        ctx, p, prof, K, N, ld_dev, bg_dev, mapping_dev, map_offset, flags, l2_dev,
+        [&](int k0, int kg) {
+            hipLaunchKernelGGL(md_stage_kernel, dim3(p.n_tiles, kg), dim3(256), 0, ctx->stream, D, N, p.n_tiles, k0, pstride,
+                               packed_dev, X_dev, ld_dev, bg_dev, tlp_dev, logq_dev, mapping_dev, map_offset, flags, p.lse, p.Zt);
+        },
+        [&](int kg) {
+            hipLaunchKernelGGL(md_gram_kernel, dim3(p.nblk * (p.nblk + 1) / 2, kg), dim3(512), gram_lds, ctx->stream, D,
+                               p.n_tiles, p.LDG, p.Zt, p.G);
+        },
+        [&](int k0, int kg) {
+            hipLaunchKernelGGL(md_unwhiten_kernel, dim3((D + 255) / 256, kg), dim3(256), 0, ctx->stream, D, p.LDG, k0, pstride,
+                               packed_dev, p.beta, p.fail, h_neg_diag_out_dev, g_neg_out_dev);
+        });
 }

@@ -30,12 +30,8 @@ template <int DP>
 static int launch_stein_finalize(gmmvi_ctx* ctx, int K, int D, int R, int N, int flags, const float* part,
                                  const float* part_m, float* H_neg, float* g_neg, const float* packed) {
     const size_t shmem = stein_finalize_lds_floats(DP, D, R) * sizeof(float);
-    static size_t attr = 64 * 1024;
-    if (shmem > attr) {
-        GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)stein_finalize_kernel<DP>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-        attr = shmem;
-    }
+    int rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)stein_finalize_kernel<DP>, shmem);
+    if (rc != GMMVI_OK) return rc;
     // the products of the explicit-inverse route use every thread; the substitution route only D of them
     const int threads = Pack<DP>::FRAGS ? 1024 : 256;
     GMMVI_PROF(ctx, "stein_finalize");
@@ -363,12 +359,8 @@ static int launch_stein_moment(gmmvi_ctx* ctx, int K, int D, const float* packed
         size_t floats = (size_t)(2 * D1 + ST::NB + 2) * SM_RS;                 // a wave's images ...
         if (floats < (size_t)16 * ST::MT * (16 * ST::NT + 1)) floats = (size_t)16 * ST::MT * (16 * ST::NT + 1);     // ... or its result tile
         const size_t shmem = 4 * floats * sizeof(float);
-        static size_t attr = 64 * 1024;
-        if (shmem > attr) {
-            GMMVI_HIP_CHECK(ctx, hipFuncSetAttribute((const void*)stein_moment_kernel<DP, VW>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-            attr = shmem;
-        }
+        rc = gmmvi_ensure_dynamic_lds(ctx, (const void*)stein_moment_kernel<DP, VW>, shmem);
+        if (rc != GMMVI_OK) return rc;
         GMMVI_PROF(ctx, "stein_partial");
         hipLaunchKernelGGL((stein_moment_kernel<DP, VW>), dim3(8 * per_xcd), dim3(256), shmem, ctx->stream, K, D, N, wave_range,
                            stacks, R, packed, X, tgrad, qgrad, ld, bg, mapping, map_offset,

@@ -397,6 +397,32 @@ def test_more_own_samples(ctx, rng):
     np.testing.assert_allclose(g.numpy(), rg, rtol=2e-2, atol=2e-2 * np.abs(rg).max())
 
 
+def test_more_own_samples_on_the_tiled_route(ctx, rng):
+    """GMMVI_OWN_SAMPLES_ONLY with a shifted mapping at D = 22, the first dimension of the tiled route (more_gram_big /
+    more_solve_big, padded width 24): F = 276, about 3 F own samples per component.  Every MORE kernel takes the weight of a
+    sample from one function (csrc/more_common.h); the other routes have own-samples tests of their own.  The bound is the one
+    of the tiled sizes above; rounding the oracle's rewards to fp32 moves it by at most 5e-6 (H) and 4e-7 (g)."""
+    from oracle import more as omore
+    k, d, n = 2, 22, 1700
+    m, x, mapping, tlp, tg, bg = _stein_inputs(rng, k, d, n)
+    logw, means, chols = upload_model(ctx, m)
+    packed, _ = ops().pack_components(ctx, means, chols)
+    xd = ctx.asarray(x)
+    ld, lp, _ = ops().mixture_eval(ctx, packed, logw, xd, d, want_ld=True, want_lp=True)
+    mp = mapping + 5
+    l2 = np.full(k, 1e-6)
+    h, g = ops().more(ctx, packed, chols, xd, ld, lp, ctx.asarray(bg), ctx.asarray(tlp), ctx.asarray(l2), d,
+                      mapping=ctx.asarray(mp, np.int32), map_offset=k - 1 - int(mp.max()), own_samples_only=True)
+    rh, rg = omore.get_expected_hessian_and_grad(m, l2, x, mp, bg, tlp, True, True)
+    h, g = h.numpy(), g.numpy()
+    assert np.all(np.isfinite(rh)) and np.all(np.isfinite(rg))
+    scale_h = np.abs(rh).max(axis=(1, 2), keepdims=True)
+    scale_g = np.abs(rg).max(axis=1, keepdims=True)
+    print("tiled own-samples deviation / scale: H %.3e, g %.3e" % ((np.abs(h - rh) / scale_h).max(), (np.abs(g - rg) / scale_g).max()))
+    assert np.all(np.abs(h - rh) <= 1e-2 * scale_h + 1e-5)
+    assert np.all(np.abs(g - rg) <= 1e-2 * scale_g + 1e-5)
+
+
 def test_more_quadratic_reward_is_exact(ctx, rng):
     """A reward that IS quadratic is recovered whatever the weights: H = -2A' form, g from the linear term."""
     from oracle import gmm as ogmm2
