@@ -27,6 +27,19 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
 
 __device__ __forceinline__ float philox_u01(uint32_t w) { return ((float)(w >> 8) + 0.5f) * (1.0f / 16777216.0f); }
 
+// ln u for u = ((w >> 8) + 0.5) * 2^-24.  From k = w >> 8 = 2^23 on, k + 0.5 has 25 significant bits: philox_u01 rounds it (to
+// 1.0 for the last k), an absolute error of up to 2^-25 in u and so in ln u ~ -(1 - u) near u = 1 -- all of it for the last k,
+// where r = sqrt(-2 ln u) came out as 0 instead of 2.4e-4, and 1e-3 of r at r = 0.005.  The rounding residual
+// (k + 0.5) - fl(k + 0.5) is 0 or +-0.5, exact in fp32: ln u = ln fl(u) + residual * 2^-24 / fl(u), second order 2^-51.
+// Below 2^23 the residual is 0 and the result is logf(u) bit for bit.
+__device__ __forceinline__ float philox_log_u01(uint32_t w) {
+    const float kf = (float)(w >> 8);
+    const float s = kf + 0.5f;
+    const float resid = (kf - s) + 0.5f;
+    const float u = s * (1.0f / 16777216.0f);
+    return logf(u) + __fdividef(resid * (1.0f / 16777216.0f), u);
+}
+
 // four standard normals for (index, block)
 __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t index, uint32_t block, uint32_t stream,
                                                float (&n)[4]) {
@@ -34,8 +47,8 @@ __device__ __forceinline__ void philox_normal4(uint64_t seed, uint64_t index, ui
                               (uint32_t)(seed >> 32));
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-        const float u1 = philox_u01(p.w[2 * h]), u2 = philox_u01(p.w[2 * h + 1]);
-        const float r = sqrtf(-2.0f * logf(u1));
+        const float u2 = philox_u01(p.w[2 * h + 1]);
+        const float r = sqrtf(-2.0f * philox_log_u01(p.w[2 * h]));
         float s, c;
         sincosf(6.283185307179586f * u2, &s, &c);
         n[2 * h] = r * c;

@@ -11,7 +11,10 @@ vectors in tests/test_oracle_philox.py.
 Stream layout (shared with gmmvi_amd/csrc/philox.h):
     key     = (seed & 0xffffffff, seed >> 32)
     counter = (index & 0xffffffff, index >> 32, block, stream)
-    words w0..w3 -> uniforms u_i = ((w_i >> 8) + 0.5) * 2**-24           (exact in fp32)
+    words w0..w3 -> uniforms u_i = ((w_i >> 8) + 0.5) * 2**-24           (exact in fp32 below 0.5; above, w_i >> 8 plus
+                                                                          one half has 25 bits and the fp32 value is the
+                                                                          nearest even one -- the device takes ln u_0 and
+                                                                          ln u_2 of the unrounded value: philox_log_u01)
     normals  (n0, n1) = BoxMuller(u0, u1), (n2, n3) = BoxMuller(u2, u3)
     BoxMuller(a, b) = sqrt(-2 ln a) * (cos(2 pi b), sin(2 pi b))
     eps[index, 4*block + j] = n_j
