@@ -1,4 +1,4 @@
-// Merge of the per-chunk partials of a component-split mixture sweep (density.hip: gridDim.y > 1):
+// Merge of the per-chunk partials of a component-split mixture sweep (density_sweep.h: gridDim.y > 1):
 //   lp[n] = log sum_r exp(lp_r[n]);  grad[n, :] = sum_r exp(lp_r[n] - lp[n]) grad_r[n, :]   (fixed order over r).
 // One element function, three users with identical arithmetic: the stand-alone launch (comm.hip, also the E2 exchange of the
 // sharded path), extra workgroups riding in the NEXT launch of the single-call iteration (a launch that exists anyway and does

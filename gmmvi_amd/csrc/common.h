@@ -11,7 +11,7 @@
 #include "iter_prep.h"
 
 // a merge of component-chunk partials (combine.h) that has not been launched yet: the single-call iteration lets the next
-// launch carry it (density.hip defers, the target / expected-log-ratio launches take it)
+// launch carry it (density.hip gmmvi_sweep_launch defers, the target / expected-log-ratio launches take it)
 struct CombineJob {
     int R = 0, N = 0, D = 0;
     long part_stride = 0;                 // floats between the parts of consecutive chunks (0: N log values, N * D gradient entries)
@@ -196,7 +196,7 @@ inline int gmmvi_padded_dim(int D) {
         default: return gmmvi_fail(ctx, GMMVI_ERR_ARG, "unsupported dimension (D must be <= 64)"); \
     }
 
-// Padded dimension from which the density sweeps run on the matrix cores with the explicit inverse (density.hip).  Measured at
+// Padded dimension from which the density sweeps run on the matrix cores with the explicit inverse (density.hip: the route choice; density_mfma.hip, density_mfma_ws.hip).  Measured at
 // K = 100, N = 10^4 (profiles/r02_notes.md): D = 50 dual sweep + target 368 -> 178 us, post-update sweep 100 -> 61 us; D = 20 and D = 10
 // are slower there (a 16-sample sub-tile pays the log-sum-exp tail four times as often per pair): they keep the scalar-fed
 // substitution kernel and the smaller block.
@@ -232,7 +232,7 @@ struct Pack {
     static constexpr int FWD = FRAGS ? ((CONST + 1 + 63) / 64) * 64 : ((CONST + 1 + 3) / 4) * 4;
     static constexpr int BWD = FWD + 64 * NF;
     // every block ends in the SWEEP STREAM: the floats a component pass of the packed
-    // two-samples-per-lane sweep reads, in the order it reads them (density.hip, subst_pk.h), each part 16-byte aligned:
+    // two-samples-per-lane sweep reads, in the order it reads them (density_pk.hip, subst_pk.h), each part 16-byte aligned:
     //   SWH  mu[DP], log-normaliser
     //   SWF  forward substitution by columns, the reciprocal of the diagonal entry in front of its column:
     //        column j = [1 / L_jj, L_{j+1,j}, ..., L_{DP-1,j}]  at SWF + swf_col(j)

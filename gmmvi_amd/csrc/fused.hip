@@ -27,7 +27,7 @@ float* carve_arena(float* base, int K, int D, int N, Arena& a) {
     return base;
 }
 
-// What density.hip reads from the context about the sweep it is asked for: which sweep of the iteration it is (profile name)
+// What density.hip (gmmvi_sweep_launch) reads from the context about the sweep it is asked for: which sweep of the iteration it is (profile name)
 // and whether the next launch carries the merge of its chunk partials.  Holds for the scope, whatever way it is left.
 struct SweepScope {
     gmmvi_ctx* ctx; const char* tag; bool defer;

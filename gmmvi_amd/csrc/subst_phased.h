@@ -1,4 +1,4 @@
-// Scalar-fed triangular substitutions with SOFTWARE-PIPELINED block loads (density.hip, padded D <= 24).
+// Scalar-fed triangular substitutions with SOFTWARE-PIPELINED block loads (density_reg.hip, padded D <= 24).
 //
 // A wave's component pass reads ~420 wave-uniform floats of the packed block through scalar loads.  Left to the compiler the
 // pass is a chain of "s_load_dwordx16 -> s_waitcnt lgkmcnt(0) -> a few multiply-adds" segments: ~24 exposed L2 round trips of

@@ -1,4 +1,4 @@
-// Scalar-fed triangular substitutions for TWO samples per lane (density.hip: mixture_eval_pk_kernel, padded D <= 24).
+// Scalar-fed triangular substitutions for TWO samples per lane (density_pk.hip: mixture_eval_pk_kernel, padded D <= 24).
 //
 // Why: a wave64 v_fma_f32 with a scalar multiplier issues once per 4 cycles per SIMD on gfx950 whatever the number of resident
 // waves (68 TFLOP/s over the chip), v_pk_fma_f32 issues at the same rate and does two multiply-adds per lane (130 TFLOP/s;

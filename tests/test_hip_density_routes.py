@@ -1,4 +1,4 @@
-"""The packed two-samples-per-lane mixture sweep (density.hip mixture_eval_pk_kernel) and the small log-sum-exp merges
+"""The packed two-samples-per-lane mixture sweep (density_pk.hip mixture_eval_pk_kernel) and the small log-sum-exp merges
 against fp64 NumPy / SciPy.
 
 From (N + 127) / 128 * K >= 4096 passes on, gmmvi_mixture_eval(_dual) runs the packed kernel: every padded dimension it is
@@ -45,9 +45,9 @@ def padded_dim(d):
 
 
 def packed_route(k, n, d, grad):
-    """The route choice of density.hip launch_mixture_eval (the block under "enough (128-sample tile, component) passes",
-    lines 1502-1518) with no GMMVI_ME_PK* knob set: the packed kernel from 4 096 passes on, at padded D <= 50, with the
-    gradient only up to padded D = 40."""
+    """The route choice of density.hip sweep_route (the block under "enough (128-sample tile, component) passes") with no
+    GMMVI_ME_PK* knob set: the packed kernel from 4 096 passes on, at padded D <= 50, with the gradient only up to padded
+    D = 40."""
     dp = padded_dim(d)
     if dp > 50 or (grad and dp > 40):
         return False

@@ -127,7 +127,7 @@ def test_mixture_eval_every_padded_dimension(ctx, rng, k, d, n, family):
 @pytest.mark.parametrize("k,d,n", [(20, 50, 2304), (17, 40, 2100), (16, 32, 2049), (33, 45, 2600)])
 def test_mixture_eval_workgroup_shared_blocks(ctx, rng, k, d, n):
     """K >= 16 and N >= 2048 with the gradient on the matrix-core dimensions: the eight waves of a workgroup share a component
-    block through LDS (density.hip mixture_eval_mfma_ws): ragged last tile, chunk merge, padded dimension (45 in 50)."""
+    block through LDS (density_mfma_ws.hip mixture_eval_mfma_ws_kernel): ragged last tile, chunk merge, padded dimension (45 in 50)."""
     m = random_gmm(rng, k, d)
     x = m.means[rng.integers(0, k, n)] + rng.normal(size=(n, d)) * 1.5
     logw, means, chols = upload_model(ctx, m)
