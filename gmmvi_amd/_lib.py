@@ -191,6 +191,8 @@ _PROTOS = {
     "gmmvi_more_blocked": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "gmmvi_more_diag": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _p, _i, _i, _p, _p, _p]),
     "gmmvi_update_components_kl": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p, _p]),
+    "gmmvi_stein_update_kl": (_i, [_p, _i, _i, _p, _p, _i, _p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p,
+                                   C.POINTER(C.c_int32)]),
     "gmmvi_update_components_kl_reference": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _f, _p, _p, _p, _p, _p, _p]),
     "gmmvi_update_components_direct": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p]),
     "gmmvi_update_components_iblr": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _f, _p, _p, _p]),

@@ -12,6 +12,10 @@
 #include <cfloat>
 #include <cstdlib>
 
+// update_kl.hip UKL_TAIL_MIN: a column of the whitened M whose tail sum of squares is at most this counts as already tridiagonal
+// (negligible against the unit diagonal of B = I + M / eta; in the fp32 subnormal range 1 / (nrm^2 - alpha x1) overflows)
+#define BLK_TAIL_MIN 1e-30f
+
 namespace {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -1842,7 +1846,7 @@ __global__ __launch_bounds__(1024) void blk_tridiag_kernel(int D, int DT, int G,
         const bool mine = g0 && i > c;
         const float tail = block_sum_nb((mine && i > c + 1) ? xi * xi : 0.f, red + 32);
         float v_here = 0.f;
-        if (!(tail > 0.f)) {                       // column already tridiagonal (NaN lands here too: handled by the search)
+        if (!(tail > BLK_TAIL_MIN)) {              // column already tridiagonal (NaN lands here too: handled by the search)
             beta = 0.f;
             if (tid == 0) te[c] = x1;
         } else {
@@ -2009,7 +2013,7 @@ __global__ __launch_bounds__(64 * NW) void blk_tridiag_reg_kernel(int D, const f
     // alpha or the untouched sub-diagonal entry to te[c]; returns v_i, sets beta_out
     auto reflector = [&](int c, float xi, float x1, float tail, int buf, float& beta_out) {
         float v_here = 0.f;
-        if (!(tail > 0.f)) {                       // column already tridiagonal (NaN lands here too: handled by the search)
+        if (!(tail > BLK_TAIL_MIN)) {              // column already tridiagonal (NaN lands here too: handled by the search)
             beta_out = 0.f;
             if (tid == 0) te[c] = x1;
         } else {

@@ -103,6 +103,27 @@ __device__ void cho_solve_vec(const float* C, float* b, int D, int ld) {
     __syncthreads();
 }
 
+// In-place inverse of the full, not necessarily symmetric matrix A by Gauss-Jordan elimination without pivoting (lane t = row t;
+// A is a positive definite matrix plus a perturbation wherever the update can succeed).  Returns false on a zero or non-finite
+// pivot; an indefinite A is inverted all the same and fails in the Cholesky factorisation that follows, as in the reference.
+__device__ bool gauss_jordan_inverse(float* A, int D, int ld) {
+    const int t = threadIdx.x;
+    for (int j = 0; j < D; ++j) {
+        const float p = A[j * ld + j];                                   // uniform: every lane reads the same element
+        if (!(fabsf(p) > 0.f) || !(fabsf(p) < FLT_MAX)) return false;
+        const float ip = 1.f / p;
+        __syncthreads();
+        if (t < D) A[j * ld + t] = (t == j) ? ip : A[j * ld + t] * ip;
+        __syncthreads();
+        if (t < D && t != j) {
+            const float f = A[t * ld + j];
+            for (int c = 0; c < D; ++c) A[t * ld + c] = (c == j) ? -f * ip : fmaf(-f, A[j * ld + c], A[t * ld + c]);
+        }
+        __syncthreads();
+    }
+    return true;
+}
+
 struct KlResult { float kl; bool ok; };
 
 // kl() of the reference (:244-333, full-covariance branch) for a linear-space eta.  Leaves chol(Q') in s.C and the
@@ -284,7 +305,7 @@ __global__ __launch_bounds__(64) void update_plain_kernel(int mode, int D, float
         matvec(s.R, s.mu, s.r, D, ld);
         if (t < D) {
             s.mun[t] = s.q[t] + step * (s.r[t] - g_neg[(size_t)k * D + t]);
-            for (int j = 0; j <= t; ++j) s.C[t * ld + j] = s.Q[t * ld + j] + step * s.R[t * ld + j];
+            for (int j = 0; j < D; ++j) s.C[t * ld + j] = s.Q[t * ld + j] + step * s.R[t * ld + j];
         }
         __syncthreads();
     } else {
@@ -315,7 +336,7 @@ __global__ __launch_bounds__(64) void update_plain_kernel(int mode, int D, float
         }
         __syncthreads();
         if (t < D) {
-            for (int j = 0; j <= t; ++j) {
+            for (int j = 0; j < D; ++j) {
                 float a = 0.f;
                 for (int c = 0; c < D; ++c) a = fmaf(row[c], s.R[c * ld + j], a);
                 s.C[t * ld + j] = s.Q[t * ld + j] + step * (s.R[t * ld + j] + 0.5f * step * a);
@@ -323,9 +344,33 @@ __global__ __launch_bounds__(64) void update_plain_kernel(int mode, int D, float
         }
         __syncthreads();
     }
-    bool success = chol_lower(s.C, D, ld);
-    if (success && mode == 0) cho_solve_vec(s.C, s.mun, D, ld);          // new_mean = new_prec^-1 new_lin (:116)
-    if (success) success = new_chol_from_precision_chol(s);              // inv + cholesky (:117-118 / :199-200)
+    // The reference inverts the new precision as it stands (tf.linalg.solve :116, tf.linalg.inv :117 / :199) and factorises the
+    // lower triangle of that inverse (:118 / :200).  For a symmetric R that is the Cholesky route below.  Under plain importance
+    // weights R is not symmetric, and neither is the new precision: a Cholesky factorisation of its lower triangle would be the
+    // update of another matrix, so the full matrix is inverted (Gauss-Jordan).
+    bool nonsym = false;
+    if (t < D)
+        for (int j = 0; j < t; ++j) nonsym |= !(s.R[t * ld + j] == s.R[j * ld + t]);      // (NaN: the pivot test rejects it)
+    nonsym = wave_any(nonsym);
+    bool success;
+    if (nonsym) {
+        success = gauss_jordan_inverse(s.C, D, ld);                      // C = new_prec^-1, the new covariance
+        if (success && mode == 0) {
+            if (t < D) s.tmp[t] = s.mun[t];
+            __syncthreads();
+            matvec(s.C, s.tmp, s.mun, D, ld);                            // new_mean = new_prec^-1 new_lin (:116)
+        }
+        if (success) {
+            if (t < D)
+                for (int j = 0; j <= t; ++j) s.Q[t * ld + j] = s.C[t * ld + j];
+            __syncthreads();
+            success = chol_lower(s.Q, D, ld);                            // :118 / :200
+        }
+    } else {
+        success = chol_lower(s.C, D, ld);
+        if (success && mode == 0) cho_solve_vec(s.C, s.mun, D, ld);      // new_mean = new_prec^-1 new_lin (:116)
+        if (success) success = new_chol_from_precision_chol(s);          // inv + cholesky (:117-118 / :199-200)
+    }
     if (success) {
         bool bad = false;
         if (t < D) {

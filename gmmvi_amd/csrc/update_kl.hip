@@ -49,6 +49,13 @@ __device__ __forceinline__ void ukl_static_for(F&& f) {
 
 typedef float ukl_v2 __attribute__((ext_vector_type(2)));
 
+// A column whose tail (the sum of squares below the sub-diagonal) is at most this counts as already tridiagonal.  Entries of
+// M below 1e-15 vanish against the unit diagonal of B = I + M / eta (eta >= 1 in every probe), while a tail in the fp32
+// subnormal range breaks the reflector: v_sqrt_f32 / v_rcp_f32 flush it (nrm = 0, beta = inf) and even the IEEE forms overflow
+// in 1 / (nrm^2 - alpha x1).  M turned NaN, and a reward of 1e-20 ... 1e-22 -- a far-away component under plain importance
+// weights -- was rejected where fp64 accepts it with a negligible step.
+#define UKL_TAIL_MIN 1e-30f
+
 // out(i, j) = sum_c fa(c, i) fb(c, j), i, j < D, by 2 x 5 register blocks (one per thread: D <= 50 gives <= 250 blocks): seven
 // LDS reads per ten multiply-adds instead of twenty
 template <int D, class FA, class FB, class FO>
@@ -389,7 +396,7 @@ __global__ __launch_bounds__(64 * NW) void update_kl_fast_kernel(int Drt, float*
                 t2 = z * z + t2;
             }
             const float tail = t2.x + t2.y;
-            if (!(tail > 0.f)) {                    // column already tridiagonal (also covers NaN: handled later)
+            if (!(tail > UKL_TAIL_MIN)) {           // column already tridiagonal (also covers NaN: handled later)
                 if (t == 0) s.te[c] = x1;
                 UKL_WSYNC();
                 return;                             // uniform: every lane computed the same tail
@@ -457,7 +464,7 @@ __global__ __launch_bounds__(64 * NW) void update_kl_fast_kernel(int Drt, float*
                 const float xj = s.M[j * ld + c];
                 tail = (j > c + 1) ? fmaf(xj, xj, tail) : tail;
             }
-            if (!(tail > 0.f)) {                        // column already tridiagonal (also covers NaN: handled later)
+            if (!(tail > UKL_TAIL_MIN)) {               // column already tridiagonal (also covers NaN: handled later)
                 if (t == 0) s.te[c] = x1;
                 continue;                               // uniform: every lane computed the same tail
             }
@@ -977,4 +984,26 @@ int gmmvi_update_components_kl_from_slab(gmmvi_ctx* ctx, int K, int D, const Ste
     return update_kl_launch(ctx, K, D, means_dev, chols_dev, H_neg_dev, g_neg_dev, slab, N, stein_flags, packed_old_dev,
                             stepsizes_dev, temperature, l2_init, last_eta_dev, l2_dev, num_received_updates_dev, success_out_dev,
                             nullptr, nullptr, packed_out_dev);
+}
+
+// Test-only: the component-update step of the single-call iteration on its own (csrc/fused.hip: gmmvi_stein_partials followed by
+// gmmvi_update_components_kl_from_slab, nothing else), so that the direct route, the in-kernel finalize prologue and the
+// finalize-then-update fallback can be compared with fp64 on their own inputs.  slab_R_out (host pointer, may be NULL) receives
+// the number of partials per component, from which the caller can restate which of the three ran.
+extern "C" int gmmvi_stein_update_kl(gmmvi_ctx* ctx, int K, int D, const float* packed_old_dev, const float* X_dev, int N,
+                                     const float* ld_dev, const float* qgrad_dev, const float* bg_dev, const float* tgrad_dev,
+                                     int stein_flags, float* H_neg_dev, float* g_neg_dev, float* means_dev, float* chols_dev,
+                                     const float* stepsizes_dev, float temperature, float l2_init, float* last_eta_dev,
+                                     float* l2_dev, float* num_received_updates_dev, int32_t* success_out_dev,
+                                     float* packed_out_dev, int32_t* slab_R_out) {
+    GMMVI_ARG_CHECK(ctx, K >= 1 && D >= 1 && D < GMMVI_MAX_DIM && !gmmvi_is_blocked_dim(D) && N >= 1);
+    GMMVI_ARG_CHECK(ctx, packed_old_dev && X_dev && ld_dev && qgrad_dev && bg_dev && tgrad_dev && H_neg_dev && g_neg_dev &&
+                             means_dev && chols_dev && stepsizes_dev && last_eta_dev && l2_dev && num_received_updates_dev);
+    SteinSlab slab{nullptr, nullptr, 0};
+    int rc = gmmvi_stein_partials(ctx, K, D, packed_old_dev, X_dev, N, ld_dev, qgrad_dev, bg_dev, tgrad_dev, stein_flags, &slab);
+    if (rc != GMMVI_OK) return rc;
+    if (slab_R_out) *slab_R_out = slab.R;
+    return gmmvi_update_components_kl_from_slab(ctx, K, D, slab, N, stein_flags, packed_old_dev, H_neg_dev, g_neg_dev, means_dev,
+                                                chols_dev, stepsizes_dev, temperature, l2_init, last_eta_dev, l2_dev,
+                                                num_received_updates_dev, success_out_dev, packed_out_dev);
 }

@@ -468,6 +468,29 @@ def update_components_kl(ctx, means, chols, h_neg, g_neg, stepsizes, temperature
     return (success, kl, probes, packed) if want_packed else (success, kl, probes)
 
 
+def stein_update_kl(ctx, packed_old, x, ld, qgrad, bg, tgrad, means, chols, stepsizes, temperature, l2_init, last_eta, l2,
+                    num_updates, self_normalized=True, explicit_estimate=False):
+    """Test-only (gmmvi_stein_update_kl): the Stein partials and the update that finishes the estimate itself, as the single-call
+    iteration runs them -> (success, packed_new, h_neg scratch, g_neg scratch, partials per component)."""
+    import ctypes
+    k, d = means.shape
+    n = x.shape[0]
+    _req(packed_old, (k, packed_stride(d)), name="packed_old"); _req(x, (n, d), name="x"); _req(ld, (k, n), name="ld")
+    _req(qgrad, (n, d), name="qgrad"); _req(bg, (n,), name="bg"); _req(tgrad, (n, d), name="tgrad")
+    _req(means, (k, d), name="means"); _req(chols, (k, d, d), name="chols"); _req(stepsizes, (k,), name="stepsizes")
+    _req(last_eta, (k,), name="last_eta"); _req(l2, (k,), name="l2"); _req(num_updates, (k,), name="num_updates")
+    flags = (_lib.SELF_NORMALIZED if self_normalized else 0) | (_lib.EXPLICIT_ESTIMATE if explicit_estimate else 0)
+    h_neg, g_neg = ctx.full((k, d, d), float("nan")), ctx.full((k, d), float("nan"))     # (stay NaN where a route never writes them)
+    success = ctx.empty((k,), np.int32)
+    packed = ctx.empty((k, packed_stride(d)))
+    r = ctypes.c_int32(0)
+    ctx.check(ctx.lib.gmmvi_stein_update_kl(ctx.handle, k, d, packed_old.ptr, x.ptr, n, ld.ptr, qgrad.ptr, bg.ptr, tgrad.ptr, flags,
+                                            h_neg.ptr, g_neg.ptr, means.ptr, chols.ptr, stepsizes.ptr, float(temperature),
+                                            float(l2_init), last_eta.ptr, l2.ptr, num_updates.ptr, success.ptr, packed.ptr,
+                                            ctypes.byref(r)))
+    return success, packed, h_neg, g_neg, int(r.value)
+
+
 def update_components_plain(ctx, mode, means, chols, h_neg, g_neg, stepsizes, l2_init, l2, num_updates):
     k, d = means.shape
     _req(means, (k, d), name="means"); _req(chols, (k, d, d), name="chols")

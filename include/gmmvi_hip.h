@@ -412,6 +412,16 @@ int gmmvi_update_components_kl_reference(gmmvi_ctx* ctx, int K, int D, float* me
                                          float temperature, float l2_init, float* last_eta_dev, float* l2_dev,
                                          float* num_received_updates_dev, int32_t* success_out_dev, float* kl_out_dev,
                                          int32_t* n_probes_out_dev);
+/* Test-only: the component-update step of the single-call iteration on its own -- the Stein moment partials of
+ * (packed_old, X, ld, qgrad, bg, tgrad) followed by the update that finishes the estimate itself (directly from the moment sums,
+ * in its finalize prologue, or after the stand-alone finalize launch).  H_neg[K,D,D] / g_neg[K,D] are scratch (written on the
+ * explicit routes only); *slab_R_out (host, may be NULL) receives the number of partials per component. */
+int gmmvi_stein_update_kl(gmmvi_ctx* ctx, int K, int D, const float* packed_old_dev, const float* X_dev, int N,
+                          const float* ld_dev, const float* qgrad_dev, const float* bg_dev, const float* tgrad_dev,
+                          int stein_flags, float* H_neg_dev, float* g_neg_dev, float* means_dev, float* chols_dev,
+                          const float* stepsizes_dev, float temperature, float l2_init, float* last_eta_dev, float* l2_dev,
+                          float* num_received_updates_dev, int32_t* success_out_dev, float* packed_out_dev,
+                          int32_t* slab_R_out);
 /* DirectNgBasedComponentUpdater (:97-141) and NgBasedComponentUpdaterIblr (:160-223). */
 int gmmvi_update_components_direct(gmmvi_ctx* ctx, int K, int D, float* means_dev, float* chols_dev,
                                    const float* H_neg_dev, const float* g_neg_dev, const float* stepsizes_dev,

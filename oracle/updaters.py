@@ -57,7 +57,7 @@ def kl(eta, old_lin, old_prec, old_inv_chol, reward_lin, reward_quad, kl_const_p
     c = _chol(new_prec)
     if c is None:                                                    # :320-324
         return FLOAT32_MAX, old_mean, old_prec, old_inv_chol
-    new_mean = cho_solve((c, True), new_lin)                         # :326
+    new_mean = cho_solve((c, True), new_lin, check_finite=False)     # :326 (a NaN in reward_lin gives a NaN mean and KL)
     new_logdet = -2.0 * np.sum(np.log(np.diag(c)))                   # :327
     cinv = _tri_inv(c)                                               # :328
     trace_term = np.sum(np.square(cinv @ old_inv_chol.T))            # :329  ||C^-1 L^-T||_F^2

@@ -1,5 +1,6 @@
-"""GPU parity of the blocked path (64 < D <= 512: config C5, D = 300) against the fp64 oracle: same entry points, the
-per-pair work on the matrix cores (csrc/blocked.hip).  Tolerances as in test_hip_kernels.py; the quadratic forms sum D
+"""GPU parity of the blocked path (50 < D <= 512 by default -- gmmvi_blocked_above() is 50, so D = 64 runs here too, and up to
+D = 64 stays register-resident only under GMMVI_BLOCKED_ABOVE=64; config C5, D = 300) against the fp64 oracle: same entry
+points, the per-pair work on the matrix cores (csrc/blocked.hip).  Tolerances as in test_hip_kernels.py; the quadratic forms sum D
 terms in fp32, so absolute errors of log-densities scale with D (stated per assertion)."""
 import os
 

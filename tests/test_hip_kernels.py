@@ -455,6 +455,8 @@ def _update_inputs(rng, k, d):
 
 @pytest.mark.parametrize("k,d", [(3, 4), (8, 20), (5, 10), (1, 2), (4, 50), (2, 64)])
 def test_update_components_kl(ctx, rng, k, d):
+    # (D = 64 takes the blocked route by default -- gmmvi_blocked_above() is 50; the register kernels at D = 51 ... 64 are run
+    # by test_hip_update.test_update_routes_for_d_51_to_64)
     m, hs, gs = _update_inputs(rng, k, d)
     m32 = ogmm.FullCovGMM(m.weights, m.means.astype(np.float32), m.covs.astype(np.float32))
     w = ogmm.GmmWrapper(m32, 0.1, 1e-12, 4)

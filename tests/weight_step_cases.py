@@ -22,8 +22,9 @@ def f32(a):
 
 
 # ---- component KL update --------------------------------------------------------------------------------------------------
-# route -> dimensions; "dense" / "reference" / "blocked" are full-covariance kernels, "diag" the three diagonal ones
-KL_ROUTES = {"dense": (4, 20, 33, 64), "reference": (4, 33), "blocked": (72, 130), "diag": (20, 600, 9000)}
+# route -> dimensions; "dense" / "reference" / "blocked" are full-covariance kernels, "diag" the three diagonal ones (D = 64 runs
+# on the blocked route: gmmvi_blocked_above() is 50 unless GMMVI_BLOCKED_ABOVE says otherwise)
+KL_ROUTES = {"dense": (4, 20, 33, 50), "reference": (4, 33), "blocked": (64, 72, 130), "diag": (20, 600, 9000)}
 KL_TEMPERATURES = (0.25, 30.0)
 KL_K = 6
 KL_STEPSIZES = np.linspace(0.05, 0.5, KL_K)
@@ -37,8 +38,9 @@ KL_SCALES = {30.0: (1.0, 64.0, 1.0, 64.0, 1.0, 64.0), 0.25: (1.0,) * 6}
 KL_SCALES_HIGHD = {30.0: (0.125, 8.0, 0.125, 8.0, 0.125, 8.0), 0.25: (1.0,) * 6}
 # (route, d, temperature) -> seed, found by first_good_kl_seed()
 KL_SEEDS = {("dense", 4, 0.25): 0, ("dense", 4, 30.0): 4, ("dense", 20, 0.25): 0, ("dense", 20, 30.0): 1, ("dense", 33, 0.25): 1,
-            ("dense", 33, 30.0): 2, ("dense", 64, 0.25): 1, ("dense", 64, 30.0): 4, ("reference", 4, 0.25): 0,
-            ("reference", 4, 30.0): 4, ("reference", 33, 0.25): 1, ("reference", 33, 30.0): 2, ("blocked", 72, 0.25): 1,
+            ("dense", 33, 30.0): 2, ("dense", 50, 0.25): 0, ("dense", 50, 30.0): 0, ("reference", 4, 0.25): 0,
+            ("reference", 4, 30.0): 4, ("reference", 33, 0.25): 1, ("reference", 33, 30.0): 2, ("blocked", 64, 0.25): 1,
+            ("blocked", 64, 30.0): 4, ("blocked", 72, 0.25): 1,
             ("blocked", 72, 30.0): 1, ("blocked", 130, 0.25): 0, ("blocked", 130, 30.0): 0, ("diag", 20, 0.25): 1,
             ("diag", 20, 30.0): 1, ("diag", 600, 0.25): 5, ("diag", 600, 30.0): 0, ("diag", 9000, 0.25): 1, ("diag", 9000, 30.0): 4}
 
