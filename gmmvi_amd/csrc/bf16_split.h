@@ -1,4 +1,4 @@
-// f32 values as sums of three bf16 values (blocked.hip: the split-operand route of the D > 50 contractions; stein.hip: the
+// f32 values as sums of three bf16 values (blocked_gemm.hip: the split-operand route of the D > 50 contractions; stein.hip: the
 // moment contraction).  x = x1 + x2 + x3 up to 2^-27 |x| (round-to-nearest splits: |x2| <= 2^-9 |x|, |x3| <= 2^-18 |x|); a product
 // x y is the sum of the six partial products x_i y_j with i + j <= 4, each exact in f32, accumulated by the bf16 matrix-core
 // instructions -- the error of an f32 contraction (tests/test_hip_blocked.py measures both routes against fp64).

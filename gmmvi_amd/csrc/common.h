@@ -61,7 +61,7 @@ struct gmmvi_ctx {
     hipEvent_t up_event[UP_SLOTS] = {};
     bool up_used[UP_SLOTS] = {};
     int up_next = 0;
-    void* bimg = nullptr;        // split bf16 images of the B operands of the blocked contractions (blocked.hip), grown on demand
+    void* bimg = nullptr;        // split bf16 images of the B operands of the blocked contractions (blocked_gemm.hip), grown on demand
     size_t bimg_bytes = 0;
     bool defer_combine = false;  // set by fused.hip around a sweep whose merge the next launch carries
     CombineJob pending;          // R > 0: partials in defer_ws wait for their merge

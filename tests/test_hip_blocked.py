@@ -1,6 +1,6 @@
 """GPU parity of the blocked path (50 < D <= 512 by default -- gmmvi_blocked_above() is 50, so D = 64 runs here too, and up to
 D = 64 stays register-resident only under GMMVI_BLOCKED_ABOVE=64; config C5, D = 300) against the fp64 oracle: same entry
-points, the per-pair work on the matrix cores (csrc/blocked.hip).  Tolerances as in test_hip_kernels.py; the quadratic forms sum D
+points, the per-pair work on the matrix cores (csrc/blocked.hip, blocked_gemm.hip).  Tolerances as in test_hip_kernels.py; the quadratic forms sum D
 terms in fp32, so absolute errors of log-densities scale with D (stated per assertion)."""
 import os
 
@@ -355,7 +355,7 @@ np.savez(sys.argv[3], ld=ld.numpy(), lp=lp.numpy(), grad=grad.numpy())
 
 def test_split_operand_route_is_as_accurate_as_the_f32_route(ctx, rng, tmp_path):
     """The default route of the blocked contractions (three bf16 planes per f32 operand, six partial products on the bf16 matrix
-    cores, f32 accumulation: csrc/blocked.hip) against the f32 matrix-core route (GMMVI_BLOCKED_F32=1, run in a child process:
+    cores, f32 accumulation: csrc/blocked_gemm.hip) against the f32 matrix-core route (GMMVI_BLOCKED_F32=1, run in a child process:
     the switch is read once per process), both measured against the fp64 oracle on the same inputs: the split route's errors
     must be of the size of the f32 route's (it drops terms below 2^-25 of a product, less than the rounding of one f32
     multiply-add).  D = 300, means far from the origin (|mu| ~ 30 sigma): x - mu is formed in f32 BEFORE the split."""

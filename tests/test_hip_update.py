@@ -1,6 +1,6 @@
 """GPU parity of the component updates against fp64 ON THEIR OWN INPUTS, on every route and seam: update_kl_fast_kernel and the
 kernel in the reference's arithmetic (csrc/update_kl.hip, csrc/update.hip), update_plain_kernel (direct, iBLR) and the blocked
-route (gmmvi_blocked_update_kl / gmmvi_blocked_update_plain, csrc/blocked.hip).
+route (gmmvi_blocked_update_kl / gmmvi_blocked_update_plain, csrc/blocked_update.hip).
 
 The device and oracle.updaters read the same fp32-representable state and rewards in every round (update_cases.py); the warm
 round starts from the fp64 result of the cold one rounded to fp32, on both sides.  Asserted per round:

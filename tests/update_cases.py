@@ -1,6 +1,6 @@
 """Inputs, fp64 reference, error measure and planted faults shared by test_hip_update.py (GPU), update_route_child.py and
 test_update_cases_cpu.py: the natural-gradient component updates (csrc/update_kl.hip, csrc/update.hip, gmmvi_blocked_update_kl /
-gmmvi_blocked_update_plain in csrc/blocked.hip) on THEIR OWN inputs.  Nothing here touches the device.
+gmmvi_blocked_update_plain in csrc/blocked_update.hip) on THEIR OWN inputs.  Nothing here touches the device.
 
 A case is a dict(id, route, law, d, k, seed, mode ("kl" / "direct" / "iblr"), temperature, H_neg, g_neg, stepsizes, rounds);
 every array is fp32-representable fp64 (f32()).  ``rounds`` is a list of dict(means, chols, last_eta, l2, num_updates) -- the

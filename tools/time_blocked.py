@@ -1,7 +1,7 @@
 """Developer tool: the blocked-path launches of one C5-shard iteration (K = 64, D = 300, N = 19 968) timed one entry point at
 a time with HIP events: density values (whitening, no Z store), density + gradient (whitening + Z store + gradient),
 Stein estimate.  GMMVI_BLOCKED_F32=1 selects the f32 matrix-core route, GMMVI_BG_DEBUG the experiment switches of
-bgemm_ws_kernel (csrc/blocked.hip)."""
+bgemm_ws_kernel (csrc/blocked_gemm.hip)."""
 import os, sys, numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gmmvi_amd.device import get_context
