@@ -16,6 +16,8 @@ MORE_BLOCKED_MIN_DIM, MORE_BLOCKED_MAX_DIM = 64, 128   # gmmvi_more_blocked: MOR
 MORE_DIAG_MAX_DIM = 1024       # gmmvi_more_diag: MORE for diagonal-covariance mixtures (F = 2 D + 1 features)
 MAX_DIM_BLOCKED = 512          # dense [K, D, D] factors (blocked kernels) exist up to here
 CUSTOM_STAGED_MAX_DIM = 120    # gmmvi_target_custom: the staged (LDS) route up to here, the direct route above
+CUSTOM_AUTODIFF_TANGENTS = 16  # GMMVI_CUSTOM_AUTODIFF_TANGENTS: tangents per pass of a differentiated user-defined target
+CUSTOM_AUTODIFF_MAX_DIM = 512  # gradient calls through a differentiated target stop here (the largest full-covariance D)
 MAX_DIM_DIAG = 131072          # diagonal-covariance mixtures: csrc/diag_sweep.hip, csrc/diag.hip
 BLOCKED_ABOVE_DEFAULT = 50     # csrc/blocked.h: D > 50 runs the blocked (MFMA) kernels
 
@@ -183,6 +185,9 @@ _PROTOS = {
     "gmmvi_custom_target_compile": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_target_release": (_i, [_p, _p]),
     "gmmvi_target_custom": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i]),
+    "gmmvi_custom_target_check_autodiff": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
+    "gmmvi_custom_target_compile_autodiff": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
+    "gmmvi_autodiff_probe": (_i, [_i, _f, _f, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),
@@ -227,6 +232,26 @@ _PROTOS = {
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS.keys())
+
+
+def _autodiff_ops():
+    """The operations of gmmvi_autodiff_probe in index order (csrc/autodiff_probe.hip).  ``_tf`` / ``_ft``: the second / the
+    first operand is a float; ``_assign``: the compound form; a trailing ``f``: the f-suffixed spelling of a function."""
+    ops = []
+    for name in ("add", "sub", "mul", "div"):
+        ops += [name, name + "_tf", name + "_ft", name + "_assign", name + "_assign_tf"]
+    ops.append("neg")
+    for name in ("lt", "le", "gt", "ge", "eq", "ne"):
+        ops += [name, name + "_tf", name + "_ft"]
+    for name in ("exp", "expm1", "log", "log1p", "sqrt", "rsqrt", "sin", "cos", "tan", "tanh", "atan", "fabs"):
+        ops += [name, name + "f"]
+    for name in ("fmax", "fmin", "pow"):
+        ops += [name, name + "_tf", name + "_ft", name + "f", name + "f_tf", name + "f_ft"]
+    ops.append("value")
+    return tuple(ops)
+
+
+AUTODIFF_OPS = _autodiff_ops()
 
 
 def load():

@@ -2,6 +2,8 @@
 // gmmvi_user_target, this file appends the wrapper kernels of custom_target_wrap.inc, compiles both with hiprtc for the device
 // of the context, loads the code object and launches the wrapper on the context's stream.  hiprtc is bound with dlopen on
 // first use: the library links without it, and only a call that needs the compiler can miss it.
+// Differentiated targets (gmmvi_custom_target_compile_autodiff): the user's source defines gmmvi_user_density instead, and the
+// dual-number text of custom_target_autodiff.inc, which defines gmmvi_user_target on top of it, goes between the two.
 #include "common.h"
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
@@ -9,6 +11,14 @@
 static const char* const kWrapText =
 #include "custom_target_wrap.inc"
     ;
+static const char* const kAutodiffText =
+#include "custom_target_autodiff.inc"
+    ;
+// Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
+// the float instantiation of the user's template finds gmmvi_value only if it is declared before the template.
+static const char* const kAutodiffPrelude = "__host__ __device__ inline float gmmvi_value(float); ";
+#define GMMVI_STR2(x) #x
+#define GMMVI_STR(x) GMMVI_STR2(x)
 
 namespace {
 struct Hiprtc {
@@ -53,17 +63,22 @@ const Hiprtc& hiprtc() {
     return h;
 }
 
-// user's text + wrapper kernels -> code object for `arch`.  GMMVI_OK, or the status with the compiler log / reason in `log`.
-int compile_source(const char* source, const char* arch, std::vector<char>& code, std::string& log) {
+// user's text (+ dual-number text) + wrapper kernels -> code object for `arch`.  GMMVI_OK, or the status with the compiler log /
+// reason in `log`.  The user's text stays first (behind one declaration on its first line): the compiler's line numbers are the
+// user's.
+int compile_source(const char* source, bool autodiff, const char* arch, std::vector<char>& code, std::string& log) {
     const Hiprtc& rt = hiprtc();
     if (!rt.why.empty()) { log = rt.why; return GMMVI_ERR_HIP; }
-    const std::string text = std::string(source) + "\n" + kWrapText;
+    const std::string text = autodiff ? std::string(kAutodiffPrelude) + source + "\n" + kAutodiffText + "\n" + kWrapText
+                                      : std::string(source) + "\n" + kWrapText;
+    const char* const entry = autodiff ? "gmmvi_user_density" : "gmmvi_user_target";
     hiprtcProgram prog = nullptr;
     hiprtcResult r = rt.create(&prog, text.c_str(), "gmmvi_user_target.hip", 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) { log = std::string("hiprtcCreateProgram: ") + rt.error_string(r); return GMMVI_ERR_HIP; }
     const std::string arch_opt = std::string("--offload-arch=") + arch;
-    const char* opts[] = {arch_opt.c_str(), "-O3", "-std=c++17"};
-    r = rt.compile(prog, 3, opts);
+    const char* opts[] = {arch_opt.c_str(), "-O3", "-std=c++17",
+                          "-DGMMVI_CUSTOM_AUTODIFF_TANGENTS=" GMMVI_STR(GMMVI_CUSTOM_AUTODIFF_TANGENTS)};   // autodiff only
+    r = rt.compile(prog, autodiff ? 4 : 3, opts);
     size_t n = 0;
     if (rt.log_size(prog, &n) == HIPRTC_SUCCESS && n > 1) {
         log.resize(n);
@@ -73,8 +88,8 @@ int compile_source(const char* source, const char* arch, std::vector<char>& code
     int rc = GMMVI_OK;
     if (r != HIPRTC_SUCCESS) {
         std::string head = std::string("user target does not compile (") + rt.error_string(r) + ")";
-        if (log.find("undeclared identifier 'gmmvi_user_target'") != std::string::npos)
-            head += ": the source does not define gmmvi_user_target";
+        if (log.find(std::string("undeclared identifier '") + entry + "'") != std::string::npos)
+            head += std::string(": the source does not define ") + entry;
         log = head + ":\n" + log;
         rc = GMMVI_ERR_ARG;
     } else {
@@ -97,6 +112,7 @@ uint64_t fnv1a(const char* s) {
 struct gmmvi_custom_target {
     uint64_t hash = 0;
     std::string source;
+    bool autodiff = false;                 // compiled through gmmvi_user_density and the dual-number text
     int refs = 0;
     hipModule_t module = nullptr;
     hipFunction_t fn[4] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad
@@ -116,12 +132,12 @@ void gmmvi_custom_targets_destroy(gmmvi_ctx* ctx) {
     ctx->custom_targets.clear();
 }
 
-extern "C" int gmmvi_custom_target_check(const char* source, const char* arch, char* log_out, size_t log_cap) {
+static int check_source(const char* what, const char* source, bool autodiff, const char* arch, char* log_out, size_t log_cap) {
     if (log_out && log_cap) log_out[0] = '\0';
-    if (!source || !arch) return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_custom_target_check: source and arch must not be NULL");
+    if (!source || !arch) return gmmvi_fail(nullptr, GMMVI_ERR_ARG, std::string(what) + ": source and arch must not be NULL");
     std::vector<char> code;
     std::string log;
-    const int rc = compile_source(source, arch, code, log);
+    const int rc = compile_source(source, autodiff, arch, code, log);
     if (log_out && log_cap) {
         const size_t n = log.size() < log_cap - 1 ? log.size() : log_cap - 1;
         memcpy(log_out, log.data(), n);
@@ -130,21 +146,30 @@ extern "C" int gmmvi_custom_target_check(const char* source, const char* arch, c
     return rc == GMMVI_OK ? rc : gmmvi_fail(nullptr, rc, log);
 }
 
-extern "C" int gmmvi_custom_target_compile(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
+extern "C" int gmmvi_custom_target_check(const char* source, const char* arch, char* log_out, size_t log_cap) {
+    return check_source("gmmvi_custom_target_check", source, false, arch, log_out, log_cap);
+}
+
+extern "C" int gmmvi_custom_target_check_autodiff(const char* source, const char* arch, char* log_out, size_t log_cap) {
+    return check_source("gmmvi_custom_target_check_autodiff", source, true, arch, log_out, log_cap);
+}
+
+// The context's modules are keyed by (hash of the source, mode): the same text compiled both ways gives two handles.
+static int compile_target(gmmvi_ctx* ctx, const char* source, bool autodiff, gmmvi_custom_target** out) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr && out != nullptr);
     *out = nullptr;
     GMMVI_ARG_CHECK(ctx, source != nullptr);
     const uint64_t hash = fnv1a(source);
     for (gmmvi_custom_target* t : ctx->custom_targets)
-        if (t->hash == hash && t->source == source) { ++t->refs; *out = t; return GMMVI_OK; }
+        if (t->hash == hash && t->autodiff == autodiff && t->source == source) { ++t->refs; *out = t; return GMMVI_OK; }
     hipDeviceProp_t prop;
     GMMVI_HIP_CHECK(ctx, hipGetDeviceProperties(&prop, ctx->device));
     std::vector<char> code;
     std::string log;
-    const int rc = compile_source(source, prop.gcnArchName, code, log);
+    const int rc = compile_source(source, autodiff, prop.gcnArchName, code, log);
     if (rc != GMMVI_OK) return gmmvi_fail(ctx, rc, log);
     gmmvi_custom_target* t = new gmmvi_custom_target();
-    t->hash = hash; t->source = source; t->refs = 1;
+    t->hash = hash; t->source = source; t->autodiff = autodiff; t->refs = 1;
     static const char* const names[4] = {"gmmvi_custom_staged_lp", "gmmvi_custom_staged_grad", "gmmvi_custom_direct_lp",
                                          "gmmvi_custom_direct_grad"};
     hipError_t e = hipSetDevice(ctx->device);
@@ -158,6 +183,14 @@ extern "C" int gmmvi_custom_target_compile(gmmvi_ctx* ctx, const char* source, g
     ctx->custom_targets.push_back(t);
     *out = t;
     return GMMVI_OK;
+}
+
+extern "C" int gmmvi_custom_target_compile(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
+    return compile_target(ctx, source, false, out);
+}
+
+extern "C" int gmmvi_custom_target_compile_autodiff(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
+    return compile_target(ctx, source, true, out);
 }
 
 extern "C" int gmmvi_custom_target_release(gmmvi_ctx* ctx, gmmvi_custom_target* t) {
@@ -184,6 +217,10 @@ extern "C" int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* t,
     if (route == 1 && D > GMMVI_CUSTOM_STAGED_MAX_DIM)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: route 1 (staged) needs D <= " +
                                                   std::to_string(GMMVI_CUSTOM_STAGED_MAX_DIM) + ", got D = " + std::to_string(D));
+    if (t->autodiff && grad_out_dev != nullptr && D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the gradient of a differentiated target needs D <= " +
+                                                  std::to_string(GMMVI_CUSTOM_AUTODIFF_MAX_DIM) + ", got D = " + std::to_string(D) +
+                                                  " (values only, or a hand-written gradient, run above)");
     const bool staged = route == 1 || (route == 0 && D <= GMMVI_CUSTOM_STAGED_MAX_DIM);
     const bool want_grad = grad_out_dev != nullptr;
     const unsigned threads = staged ? 64u : 256u;

@@ -1,0 +1,184 @@
+R"GMMVI_AD(
+// ---- forward-mode differentiation of a user-defined density (csrc/custom_target.hip puts this text between the user's source
+// and the wrapper kernels; contract: include/gmmvi_hip.h, "differentiated user-defined targets") --------------------------------
+// The text above defines   template <class T, class X> __device__ T gmmvi_user_density(X x, int D, const float* params);
+// This text defines the dual number the library instantiates T with on a gradient call (a value and W tangents), the view X
+// that seeds it, and gmmvi_user_target on top of the user's function, which is what the wrapper kernels call.
+// GMMVI_CUSTOM_AUTODIFF_TANGENTS comes from include/gmmvi_hip.h (the run-time compiler gets it as a -D option).
+//
+// Tie rules: fabs has tangent 0 at +-0; fmax and fmin take the first operand's tangent on a tie; comparisons look at the values
+// only, so a branch on a comparison differentiates the branch taken.  sqrt and rsqrt at 0 and log at 0 have infinite
+// derivatives, as in IEEE arithmetic.  There is no conversion from a dual to float: gmmvi_value(t) is the only way down.
+
+namespace gmmvi_ad {
+
+constexpr int W = GMMVI_CUSTOM_AUTODIFF_TANGENTS;
+
+#define GMMVI_AD_FN __host__ __device__ __forceinline__
+#define GMMVI_AD_EACH _Pragma("unroll") for (int j = 0; j < W; ++j)
+
+GMMVI_AD_FN float rsqrt_value(float a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return ::rsqrtf(a);
+#else
+    return 1.f / ::sqrtf(a);
+#endif
+}
+
+struct Dual {
+    float v;
+    float d[W];
+    Dual() = default;
+    GMMVI_AD_FN Dual(float value) : v(value) { GMMVI_AD_EACH d[j] = 0.f; }      // a constant: every tangent is 0
+};
+
+// value `v`, tangents s * a.d
+GMMVI_AD_FN Dual chain(float v, float s, const Dual& a) {
+    Dual r; r.v = v;
+    GMMVI_AD_EACH r.d[j] = s * a.d[j];
+    return r;
+}
+
+// ---- arithmetic ------------------------------------------------------------------------------------------------------------
+GMMVI_AD_FN Dual operator-(const Dual& a) { Dual r; r.v = -a.v; GMMVI_AD_EACH r.d[j] = -a.d[j]; return r; }
+GMMVI_AD_FN Dual operator+(const Dual& a) { return a; }
+
+GMMVI_AD_FN Dual operator+(const Dual& a, const Dual& b) { Dual r; r.v = a.v + b.v; GMMVI_AD_EACH r.d[j] = a.d[j] + b.d[j]; return r; }
+GMMVI_AD_FN Dual operator+(const Dual& a, float b) { Dual r = a; r.v = a.v + b; return r; }
+GMMVI_AD_FN Dual operator+(float a, const Dual& b) { Dual r = b; r.v = a + b.v; return r; }
+
+GMMVI_AD_FN Dual operator-(const Dual& a, const Dual& b) { Dual r; r.v = a.v - b.v; GMMVI_AD_EACH r.d[j] = a.d[j] - b.d[j]; return r; }
+GMMVI_AD_FN Dual operator-(const Dual& a, float b) { Dual r = a; r.v = a.v - b; return r; }
+GMMVI_AD_FN Dual operator-(float a, const Dual& b) { Dual r; r.v = a - b.v; GMMVI_AD_EACH r.d[j] = -b.d[j]; return r; }
+
+GMMVI_AD_FN Dual operator*(const Dual& a, const Dual& b) {
+    Dual r; r.v = a.v * b.v;
+    GMMVI_AD_EACH r.d[j] = a.d[j] * b.v + a.v * b.d[j];
+    return r;
+}
+GMMVI_AD_FN Dual operator*(const Dual& a, float b) { return chain(a.v * b, b, a); }
+GMMVI_AD_FN Dual operator*(float a, const Dual& b) { return chain(a * b.v, a, b); }
+
+GMMVI_AD_FN Dual operator/(const Dual& a, const Dual& b) {
+    Dual r; r.v = a.v / b.v;
+    const float inv = 1.f / b.v;
+    GMMVI_AD_EACH r.d[j] = (a.d[j] - r.v * b.d[j]) * inv;
+    return r;
+}
+GMMVI_AD_FN Dual operator/(const Dual& a, float b) { return chain(a.v / b, 1.f / b, a); }
+GMMVI_AD_FN Dual operator/(float a, const Dual& b) { const float v = a / b.v; return chain(v, -v / b.v, b); }
+
+GMMVI_AD_FN Dual& operator+=(Dual& a, const Dual& b) { a = a + b; return a; }
+GMMVI_AD_FN Dual& operator+=(Dual& a, float b) { a.v += b; return a; }
+GMMVI_AD_FN Dual& operator-=(Dual& a, const Dual& b) { a = a - b; return a; }
+GMMVI_AD_FN Dual& operator-=(Dual& a, float b) { a.v -= b; return a; }
+GMMVI_AD_FN Dual& operator*=(Dual& a, const Dual& b) { a = a * b; return a; }
+GMMVI_AD_FN Dual& operator*=(Dual& a, float b) { a = a * b; return a; }
+GMMVI_AD_FN Dual& operator/=(Dual& a, const Dual& b) { a = a / b; return a; }
+GMMVI_AD_FN Dual& operator/=(Dual& a, float b) { a = a / b; return a; }
+
+// ---- comparisons: on the values ------------------------------------------------------------------------------------------------
+#define GMMVI_AD_COMPARE(op)                                                             \
+    GMMVI_AD_FN bool operator op(const Dual& a, const Dual& b) { return a.v op b.v; }    \
+    GMMVI_AD_FN bool operator op(const Dual& a, float b) { return a.v op b; }            \
+    GMMVI_AD_FN bool operator op(float a, const Dual& b) { return a op b.v; }
+GMMVI_AD_COMPARE(<)
+GMMVI_AD_COMPARE(<=)
+GMMVI_AD_COMPARE(>)
+GMMVI_AD_COMPARE(>=)
+GMMVI_AD_COMPARE(==)
+GMMVI_AD_COMPARE(!=)
+#undef GMMVI_AD_COMPARE
+
+// ---- functions (each also under its f-suffixed name, below) ---------------------------------------------------------------------
+GMMVI_AD_FN Dual exp(const Dual& a) { const float v = ::expf(a.v); return chain(v, v, a); }
+GMMVI_AD_FN Dual expm1(const Dual& a) { return chain(::expm1f(a.v), ::expf(a.v), a); }
+GMMVI_AD_FN Dual log(const Dual& a) { return chain(::logf(a.v), 1.f / a.v, a); }
+GMMVI_AD_FN Dual log1p(const Dual& a) { return chain(::log1pf(a.v), 1.f / (1.f + a.v), a); }
+GMMVI_AD_FN Dual sqrt(const Dual& a) { const float v = ::sqrtf(a.v); return chain(v, 0.5f / v, a); }
+GMMVI_AD_FN Dual rsqrt(const Dual& a) { const float v = rsqrt_value(a.v); return chain(v, -0.5f * v / a.v, a); }
+GMMVI_AD_FN Dual sin(const Dual& a) { return chain(::sinf(a.v), ::cosf(a.v), a); }
+GMMVI_AD_FN Dual cos(const Dual& a) { return chain(::cosf(a.v), -::sinf(a.v), a); }
+GMMVI_AD_FN Dual tan(const Dual& a) { const float v = ::tanf(a.v); return chain(v, 1.f + v * v, a); }
+GMMVI_AD_FN Dual tanh(const Dual& a) {
+    const float e = ::expf(-2.f * ::fabsf(a.v));                   // sech^2 = 4 e / (1 + e)^2: no cancellation at large |a|
+    return chain(::tanhf(a.v), 4.f * e / ((1.f + e) * (1.f + e)), a);
+}
+GMMVI_AD_FN Dual atan(const Dual& a) { return chain(::atanf(a.v), 1.f / (1.f + a.v * a.v), a); }
+GMMVI_AD_FN Dual fabs(const Dual& a) { return chain(::fabsf(a.v), a.v > 0.f ? 1.f : (a.v < 0.f ? -1.f : 0.f), a); }
+
+// the first operand's tangent unless the second one is strictly the winner (or the first is a NaN, which fmaxf drops)
+GMMVI_AD_FN Dual fmax(const Dual& a, const Dual& b) {
+    const bool second = b.v > a.v || a.v != a.v;
+    Dual r = second ? b : a; r.v = ::fmaxf(a.v, b.v); return r;
+}
+GMMVI_AD_FN Dual fmin(const Dual& a, const Dual& b) {
+    const bool second = b.v < a.v || a.v != a.v;
+    Dual r = second ? b : a; r.v = ::fminf(a.v, b.v); return r;
+}
+GMMVI_AD_FN Dual fmax(const Dual& a, float b) { return fmax(a, Dual(b)); }
+GMMVI_AD_FN Dual fmax(float a, const Dual& b) { return fmax(Dual(a), b); }
+GMMVI_AD_FN Dual fmin(const Dual& a, float b) { return fmin(a, Dual(b)); }
+GMMVI_AD_FN Dual fmin(float a, const Dual& b) { return fmin(Dual(a), b); }
+
+// a^b, b a constant: tangent b a^(b - 1) da, and 0 for b = 0 whatever a is
+GMMVI_AD_FN Dual pow(const Dual& a, float b) {
+    return chain(::powf(a.v, b), b == 0.f ? 0.f : b * ::powf(a.v, b - 1.f), a);
+}
+// a^b: b a^(b - 1) da + a^b ln(a) db; a direction in which b does not move takes no part of ln(a) (a <= 0 stays usable there)
+GMMVI_AD_FN Dual pow(const Dual& a, const Dual& b) {
+    Dual r; r.v = ::powf(a.v, b.v);
+    const float da = b.v == 0.f ? 0.f : b.v * ::powf(a.v, b.v - 1.f);
+    const float db = r.v * ::logf(a.v);
+    GMMVI_AD_EACH r.d[j] = da * a.d[j] + (b.d[j] == 0.f ? 0.f : db * b.d[j]);
+    return r;
+}
+GMMVI_AD_FN Dual pow(float a, const Dual& b) { return pow(Dual(a), b); }
+
+#define GMMVI_AD_ALIAS1(name) GMMVI_AD_FN Dual name##f(const Dual& a) { return name(a); }
+GMMVI_AD_ALIAS1(exp) GMMVI_AD_ALIAS1(expm1) GMMVI_AD_ALIAS1(log) GMMVI_AD_ALIAS1(log1p) GMMVI_AD_ALIAS1(sqrt) GMMVI_AD_ALIAS1(rsqrt)
+GMMVI_AD_ALIAS1(sin) GMMVI_AD_ALIAS1(cos) GMMVI_AD_ALIAS1(tan) GMMVI_AD_ALIAS1(tanh) GMMVI_AD_ALIAS1(atan) GMMVI_AD_ALIAS1(fabs)
+#undef GMMVI_AD_ALIAS1
+#define GMMVI_AD_ALIAS2(name)                                                              \
+    GMMVI_AD_FN Dual name##f(const Dual& a, const Dual& b) { return name(a, b); }          \
+    GMMVI_AD_FN Dual name##f(const Dual& a, float b) { return name(a, b); }                \
+    GMMVI_AD_FN Dual name##f(float a, const Dual& b) { return name(a, b); }
+GMMVI_AD_ALIAS2(fmax) GMMVI_AD_ALIAS2(fmin) GMMVI_AD_ALIAS2(pow)
+#undef GMMVI_AD_ALIAS2
+
+GMMVI_AD_FN float gmmvi_value(const Dual& a) { return a.v; }
+
+// What a gradient call passes as x: reading entry i builds {x[i], e_(i - first)}, so the seeded input is never stored.
+struct Seed {
+    const float* x;
+    int first;
+    GMMVI_AD_FN Dual operator[](int i) const {
+        Dual r; r.v = x[i];
+        GMMVI_AD_EACH r.d[j] = i - first == j ? 1.f : 0.f;
+        return r;
+    }
+};
+
+}  // namespace gmmvi_ad
+
+// (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there)
+__host__ __device__ inline float gmmvi_value(float a) { return a; }
+
+#ifndef GMMVI_AD_NO_ADAPTER
+// The function of the wrapper kernels on top of the user's: values by one float instantiation; the gradient by ceil(D / W)
+// passes of the dual instantiation, pass `first` carrying d / d x[first .. first + W).
+__device__ __forceinline__ float gmmvi_user_target(const float* x, int D, const float* params, float* grad) {
+    if (!grad) return gmmvi_user_density<float, const float*>(x, D, params);
+    float value = 0.f;
+    for (int first = 0; first < D; first += gmmvi_ad::W) {
+        const gmmvi_ad::Dual r = gmmvi_user_density<gmmvi_ad::Dual, gmmvi_ad::Seed>(gmmvi_ad::Seed{x, first}, D, params);
+        if (first == 0) value = r.v;
+        _Pragma("unroll") for (int j = 0; j < gmmvi_ad::W; ++j)
+            if (first + j < D) grad[first + j] = r.d[j];
+    }
+    return value;
+}
+#endif
+#undef GMMVI_AD_EACH
+#undef GMMVI_AD_FN
+)GMMVI_AD"

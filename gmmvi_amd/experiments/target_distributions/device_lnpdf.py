@@ -8,6 +8,13 @@ The target is HIP source text that defines
 (contract: include/gmmvi_hip.h).  It is compiled at run time for the device of the context and evaluated by the
 library's wrapper kernels (csrc/custom_target.hip): the samples never leave the device, and the single-call and the sharded
 iteration take it as target kind 5.
+
+``DeviceAutodiffLNPDF`` takes the log density alone,
+
+    template <class T, class X> __device__ T gmmvi_user_density(X x, int D, const float* params);
+
+and the library differentiates it in forward mode (csrc/custom_target_autodiff.inc): upstream's "write log_density, the framework
+differentiates it" (SampleSelector.get_target_grads) on the device.
 """
 import numpy as np
 
@@ -44,7 +51,10 @@ class DeviceLNPDF(LNPDF):
         self.has_gradient = bool(has_gradient)
         self._num_dimensions = int(num_dimensions)
         self._params_dev = None if params is None or params.size == 0 else self.ctx.asarray(params)
-        self._handle = hip_ops.custom_target_compile(self.ctx, self.source)
+        self._handle = self._compile()
+
+    def _compile(self):
+        return hip_ops.custom_target_compile(self.ctx, self.source)
 
     def get_num_dimensions(self):
         return self._num_dimensions
@@ -69,3 +79,28 @@ class _DeviceLNPDFWithGradient(DeviceLNPDF):
         """Descriptor for the single-call and the sharded iteration (optimization/fused.py, sharded.py)."""
         return _lib.TargetSpec(kind=5, custom=self._handle.ptr,
                                custom_params=None if self._params_dev is None else self._params_dev.ptr)
+
+
+class DeviceAutodiffLNPDF(_DeviceLNPDFWithGradient):
+    """``DeviceAutodiffLNPDF(source, num_dimensions, params=None)``: ``source`` defines ``gmmvi_user_density``, the log density
+    as a template over the number type (contract and the functions it may call: include/gmmvi_hip.h), and the gradient comes
+    from the library's dual numbers, ``ceil(D / _lib.CUSTOM_AUTODIFF_TANGENTS)`` passes per sample.  Everything a
+    ``DeviceLNPDF`` with a hand-written gradient does, this does: Stein and MORE estimators, target kind 5 in both plans."""
+
+    # the gradient costs passes the value call does not: an estimator that reads no target gradients (MORE) gets values only
+    # (SampleSelector.get_target_grads)
+    gradient_on_demand = True
+
+    def __init__(self, source, num_dimensions, params=None):
+        try:
+            too_large = int(num_dimensions) == num_dimensions and int(num_dimensions) > _lib.CUSTOM_AUTODIFF_MAX_DIM
+        except (TypeError, ValueError):
+            too_large = False
+        if too_large:
+            raise ValueError(f"num_dimensions must be <= {_lib.CUSTOM_AUTODIFF_MAX_DIM} for a differentiated target, got "
+                             f"{num_dimensions}: the gradient costs ceil(D / {_lib.CUSTOM_AUTODIFF_TANGENTS}) passes per sample; "
+                             "above that, write the gradient by hand and use DeviceLNPDF")
+        super().__init__(source, num_dimensions, params, has_gradient=True)
+
+    def _compile(self):
+        return hip_ops.custom_target_compile(self.ctx, self.source, autodiff=True)

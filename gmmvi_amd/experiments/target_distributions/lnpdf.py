@@ -18,8 +18,9 @@ class LNPDF:
 
     def log_density_and_grad(self, x):
         raise NotImplementedError(
-            "this target provides no gradient: implement log_density_and_grad (the MI355X build has no autodiff; "
-            "the reference's GradientTape fallback, sample_selector.py:74-77, does not exist here)")
+            "this target provides no gradient: implement log_density_and_grad (the MI355X build has no autodiff of a "
+            "Python function; the reference's GradientTape fallback, sample_selector.py:74-77, does not exist here; a "
+            "density written as a device function is differentiated: DeviceAutodiffLNPDF)")
 
     def get_num_dimensions(self) -> int:
         raise NotImplementedError

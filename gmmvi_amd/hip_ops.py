@@ -101,6 +101,15 @@ def custom_target_check(source, arch="gfx950"):
     return int(rc), log.value.decode(errors="replace")
 
 
+def custom_target_check_autodiff(source, arch="gfx950"):
+    """custom_target_check for a source that defines ``gmmvi_user_density`` (the log density only; the library's dual-number
+    text differentiates it).  -> (status, compiler log)."""
+    import ctypes as C
+    log = C.create_string_buffer(1 << 16)
+    rc = _lib.load().gmmvi_custom_target_check_autodiff(str(source).encode(), str(arch).encode(), log, len(log))
+    return int(rc), log.value.decode(errors="replace")
+
+
 class CustomTarget:
     """A compiled user target of a context (gmmvi_custom_target); released with the object."""
 
@@ -120,12 +129,14 @@ class CustomTarget:
             pass
 
 
-def custom_target_compile(ctx, source):
-    """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  A source that does
-    not compile raises GmmviError with the compiler log."""
+def custom_target_compile(ctx, source, autodiff=False):
+    """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  autodiff: the source
+    defines ``gmmvi_user_density`` and the library differentiates it.  A source that does not compile raises GmmviError with
+    the compiler log."""
     import ctypes as C
     h = C.c_void_p()
-    ctx.check(ctx.lib.gmmvi_custom_target_compile(ctx.handle, str(source).encode(), C.byref(h)))
+    compile_fn = ctx.lib.gmmvi_custom_target_compile_autodiff if autodiff else ctx.lib.gmmvi_custom_target_compile
+    ctx.check(compile_fn(ctx.handle, str(source).encode(), C.byref(h)))
     return CustomTarget(ctx, h)
 
 

@@ -35,11 +35,14 @@ class SampleSelector:
 
     def get_target_grads(self, samples):
         """sample_selector.py:69-78 -> (gradient, target).  Built-in targets evaluate log-density and gradient in one
-        fused kernel; user targets must provide log_density_and_grad (there is no autodiff here) -- unless the estimator
+        fused kernel; Python user targets must provide log_density_and_grad (no autodiff of Python code here) -- unless the estimator
         reads no gradients and the target's class leaves LNPDF.log_density_and_grad alone: then log_density is evaluated and
-        the gradient block of the sample database is zeros."""
+        the gradient block of the sample database is zeros.  A target whose gradient is derived from its density at a cost
+        (DeviceAutodiffLNPDF: ``gradient_on_demand``) is treated the same way under such an estimator."""
         ctx = self.model.ctx
-        if not self.estimator_uses_target_gradients and not _overrides_log_density_and_grad(self.target_distribution):
+        values_only = (not _overrides_log_density_and_grad(self.target_distribution)
+                       or getattr(self.target_distribution, "gradient_on_demand", False))
+        if not self.estimator_uses_target_gradients and values_only:
             target = ctx.asarray(self.target_distribution.log_density(samples))
             return ctx.zeros((samples.shape[0], self.model.num_dimensions)), target
         target, gradient = self.target_distribution.log_density_and_grad(samples)

@@ -328,6 +328,51 @@ int gmmvi_custom_target_release(gmmvi_ctx* ctx, gmmvi_custom_target* target);   
 int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
                         const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int route);
 
+/* ---- differentiated user-defined targets: density in, gradient out -------------------------------------------------------------
+ * The counterpart of upstream's GradientTape over a user's log_density (SampleSelector.get_target_grads): the source defines the
+ * log density only, as a template,
+ *
+ *     template <class T, class X>
+ *     __device__ T gmmvi_user_density(X x, int D, const float* params);
+ *
+ *   - x[i] yields a T for 0 <= i < D; params: the target's own device array, or NULL; the function returns the log density;
+ *   - it is pure per sample under the rules of gmmvi_user_target above: no barriers, no LDS, no atomics, no writes to memory
+ *     that is not its own locals; the same flags; no names that begin with gmmvi_ other than gmmvi_user_density;
+ *   - for a value call the library instantiates T = float, X = const float*;
+ *   - for a gradient call T is the library's dual number, a value and GMMVI_CUSTOM_AUTODIFF_TANGENTS tangents, and X is a view
+ *     that returns {x[i], e_(i - first)} on read: the seeded input is never stored per lane.
+ * The library puts its dual-number text (csrc/custom_target_autodiff.inc) and then the wrapper kernels behind the source; the
+ * source stays first, so the compiler's line numbers are the user's, and the overloads are found by argument-dependent lookup
+ * when the template is instantiated (one declaration, gmmvi_value(float), goes in front of the source's first line, on that
+ * line: a float has no namespace for that lookup).  In this mode, and in no other, the compiler is also given
+ * -DGMMVI_CUSTOM_AUTODIFF_TANGENTS=<W>, so a text can tell the modes apart.  On a T the text defines
+ *   - + - * / and += -= *= /= between T and T, T and float, float and T; unary minus;
+ *   - < <= > >= == !=, decided on the values;
+ *   - exp expm1 log log1p sqrt rsqrt sin cos tan tanh atan fabs fmax fmin, pow(T, float) and pow(T, T), each also under its
+ *     f-suffixed name (expf, ...);
+ *   - gmmvi_value(t): the float value of a float and of a dual.
+ * A float converts to a T (a constant: all tangents 0); a T does not convert to float, so a function outside this list, such
+ * as lgammaf or erff, on a T is a compile error (GMMVI_ERR_ARG with the compiler log, as for any source).
+ * Tie rules: fabs has tangent 0 at +-0; fmax and fmin take the first operand's tangent on a tie; a branch on a comparison
+ * differentiates the branch taken.  pow(T, T) takes no part of ln(a) in a direction in which the exponent does not move;
+ * sqrt, rsqrt and log at 0 have the infinite derivatives of IEEE arithmetic.
+ * The gradient takes ceil(D / W) passes of the dual instantiation, W = GMMVI_CUSTOM_AUTODIFF_TANGENTS, pass `first` writing
+ * grad[first + j] for first + j < D; the value is that of the first pass.  That is ceil(D / W) * (1 + W) value evaluations per
+ * sample, so a gradient call through such a handle is capped at GMMVI_CUSTOM_AUTODIFF_MAX_DIM; a value call is not. */
+#define GMMVI_CUSTOM_AUTODIFF_TANGENTS 16
+#define GMMVI_CUSTOM_AUTODIFF_MAX_DIM 512  /* the largest full-covariance dimension */
+/* gmmvi_custom_target_check / _compile for a source that defines gmmvi_user_density (a source without it: GMMVI_ERR_ARG, the
+ * log names it).  The handle is an ordinary gmmvi_custom_target: gmmvi_target_custom launches it (a gradient pointer with
+ * D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM: GMMVI_ERR_ARG before any launch), target kind 5 takes it, gmmvi_custom_target_release
+ * releases it.  The mode is part of the context's key: the same text compiled both ways gives two handles. */
+int gmmvi_custom_target_check_autodiff(const char* source, const char* arch, char* log_out, size_t log_cap);
+int gmmvi_custom_target_compile_autodiff(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out);
+/* One operation of the dual-number text on the host (no device, no context): operands {a, da} and {b, db} (a float operand
+ * of the operation ignores its tangent, a unary operation ignores b), *value and *tangent receive the result.  op indexes the
+ * operations in the order of csrc/autodiff_probe.hip (gmmvi_amd/_lib.py AUTODIFF_OPS names them); comparisons give 1 or 0
+ * with tangent 0.  An unknown op or a NULL output: GMMVI_ERR_ARG. */
+int gmmvi_autodiff_probe(int op, float a, float da, float b, float db, float* value, float* tangent);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
