@@ -4,7 +4,12 @@
 // first use: the library links without it, and only a call that needs the compiler can miss it.
 // Differentiated targets (gmmvi_custom_target_compile_autodiff): the user's source defines gmmvi_user_density instead, and the
 // dual-number text of custom_target_autodiff.inc, which defines gmmvi_user_target on top of it, goes between the two.
+// Targets summed over a data set (gmmvi_custom_target_compile_data): the user's source defines gmmvi_user_row and
+// gmmvi_user_prior; behind it go the dual-number text without its adapter, the tile mover of the wrapper text, the Feistel
+// stream (feistel.h and philox.h, made one string by the Makefile) and the kernels of custom_target_data.inc, which
+// gmmvi_target_custom_data launches.
 #include "common.h"
+#include "feistel.h"
 #include <hip/hiprtc.h>
 #include <dlfcn.h>
 
@@ -14,11 +19,19 @@ static const char* const kWrapText =
 static const char* const kAutodiffText =
 #include "custom_target_autodiff.inc"
     ;
+static const char* const kDataText =
+    "using __hip_internal::uint32_t; using __hip_internal::uint64_t;\n"    // the run-time compiler has no <cstdint>
+#include "build/feistel_text.inc"
+#include "custom_target_data.inc"
+    ;
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
 // the float instantiation of the user's template finds gmmvi_value only if it is declared before the template.
 static const char* const kAutodiffPrelude = "__host__ __device__ inline float gmmvi_value(float); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
+
+enum Mode { MODE_HAND = 0, MODE_AUTODIFF = 1, MODE_DATA = 2 };   // what the source defines: gmmvi_user_target; gmmvi_user_density;
+                                                                 // gmmvi_user_row and gmmvi_user_prior
 
 namespace {
 struct Hiprtc {
@@ -66,19 +79,22 @@ const Hiprtc& hiprtc() {
 // user's text (+ dual-number text) + wrapper kernels -> code object for `arch`.  GMMVI_OK, or the status with the compiler log /
 // reason in `log`.  The user's text stays first (behind one declaration on its first line): the compiler's line numbers are the
 // user's.
-int compile_source(const char* source, bool autodiff, const char* arch, std::vector<char>& code, std::string& log) {
+int compile_source(const char* source, Mode mode, const char* arch, std::vector<char>& code, std::string& log) {
     const Hiprtc& rt = hiprtc();
     if (!rt.why.empty()) { log = rt.why; return GMMVI_ERR_HIP; }
-    const std::string text = autodiff ? std::string(kAutodiffPrelude) + source + "\n" + kAutodiffText + "\n" + kWrapText
-                                      : std::string(source) + "\n" + kWrapText;
-    const char* const entry = autodiff ? "gmmvi_user_density" : "gmmvi_user_target";
+    std::string text = mode == MODE_HAND ? std::string(source) : std::string(kAutodiffPrelude) + source + "\n" + kAutodiffText;
+    text += std::string("\n") + kWrapText;
+    if (mode == MODE_DATA) text += std::string("\n") + kDataText;
+    static const char* const entries[3][2] = {{"gmmvi_user_target", nullptr}, {"gmmvi_user_density", nullptr},
+                                              {"gmmvi_user_row", "gmmvi_user_prior"}};
     hiprtcProgram prog = nullptr;
     hiprtcResult r = rt.create(&prog, text.c_str(), "gmmvi_user_target.hip", 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) { log = std::string("hiprtcCreateProgram: ") + rt.error_string(r); return GMMVI_ERR_HIP; }
     const std::string arch_opt = std::string("--offload-arch=") + arch;
     const char* opts[] = {arch_opt.c_str(), "-O3", "-std=c++17",
-                          "-DGMMVI_CUSTOM_AUTODIFF_TANGENTS=" GMMVI_STR(GMMVI_CUSTOM_AUTODIFF_TANGENTS)};   // autodiff only
-    r = rt.compile(prog, autodiff ? 4 : 3, opts);
+                          "-DGMMVI_CUSTOM_AUTODIFF_TANGENTS=" GMMVI_STR(GMMVI_CUSTOM_AUTODIFF_TANGENTS),   // not MODE_HAND
+                          "-DGMMVI_AD_NO_ADAPTER", "-DGMMVI_WRAP_TILE_ONLY"};                              // MODE_DATA only
+    r = rt.compile(prog, mode == MODE_HAND ? 3 : mode == MODE_AUTODIFF ? 4 : 6, opts);
     size_t n = 0;
     if (rt.log_size(prog, &n) == HIPRTC_SUCCESS && n > 1) {
         log.resize(n);
@@ -88,8 +104,9 @@ int compile_source(const char* source, bool autodiff, const char* arch, std::vec
     int rc = GMMVI_OK;
     if (r != HIPRTC_SUCCESS) {
         std::string head = std::string("user target does not compile (") + rt.error_string(r) + ")";
-        if (log.find(std::string("undeclared identifier '") + entry + "'") != std::string::npos)
-            head += std::string(": the source does not define ") + entry;
+        for (const char* entry : entries[mode])
+            if (entry && log.find(std::string("undeclared identifier '") + entry + "'") != std::string::npos)
+                head += std::string(": the source does not define ") + entry;
         log = head + ":\n" + log;
         rc = GMMVI_ERR_ARG;
     } else {
@@ -112,10 +129,10 @@ uint64_t fnv1a(const char* s) {
 struct gmmvi_custom_target {
     uint64_t hash = 0;
     std::string source;
-    bool autodiff = false;                 // compiled through gmmvi_user_density and the dual-number text
+    Mode mode = MODE_HAND;
     int refs = 0;
     hipModule_t module = nullptr;
-    hipFunction_t fn[4] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad
+    hipFunction_t fn[6] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad
 };
 
 static std::vector<gmmvi_custom_target*>::iterator find_target(gmmvi_ctx* ctx, const gmmvi_custom_target* t) {
@@ -132,12 +149,12 @@ void gmmvi_custom_targets_destroy(gmmvi_ctx* ctx) {
     ctx->custom_targets.clear();
 }
 
-static int check_source(const char* what, const char* source, bool autodiff, const char* arch, char* log_out, size_t log_cap) {
+static int check_source(const char* what, const char* source, Mode mode, const char* arch, char* log_out, size_t log_cap) {
     if (log_out && log_cap) log_out[0] = '\0';
     if (!source || !arch) return gmmvi_fail(nullptr, GMMVI_ERR_ARG, std::string(what) + ": source and arch must not be NULL");
     std::vector<char> code;
     std::string log;
-    const int rc = compile_source(source, autodiff, arch, code, log);
+    const int rc = compile_source(source, mode, arch, code, log);
     if (log_out && log_cap) {
         const size_t n = log.size() < log_cap - 1 ? log.size() : log_cap - 1;
         memcpy(log_out, log.data(), n);
@@ -147,34 +164,42 @@ static int check_source(const char* what, const char* source, bool autodiff, con
 }
 
 extern "C" int gmmvi_custom_target_check(const char* source, const char* arch, char* log_out, size_t log_cap) {
-    return check_source("gmmvi_custom_target_check", source, false, arch, log_out, log_cap);
+    return check_source("gmmvi_custom_target_check", source, MODE_HAND, arch, log_out, log_cap);
 }
 
 extern "C" int gmmvi_custom_target_check_autodiff(const char* source, const char* arch, char* log_out, size_t log_cap) {
-    return check_source("gmmvi_custom_target_check_autodiff", source, true, arch, log_out, log_cap);
+    return check_source("gmmvi_custom_target_check_autodiff", source, MODE_AUTODIFF, arch, log_out, log_cap);
 }
 
-// The context's modules are keyed by (hash of the source, mode): the same text compiled both ways gives two handles.
-static int compile_target(gmmvi_ctx* ctx, const char* source, bool autodiff, gmmvi_custom_target** out) {
+extern "C" int gmmvi_custom_target_check_data(const char* source, const char* arch, char* log_out, size_t log_cap) {
+    return check_source("gmmvi_custom_target_check_data", source, MODE_DATA, arch, log_out, log_cap);
+}
+
+// The context's modules are keyed by (hash of the source, mode): the same text compiled in two modes gives two handles.
+static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_custom_target** out) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr && out != nullptr);
     *out = nullptr;
     GMMVI_ARG_CHECK(ctx, source != nullptr);
     const uint64_t hash = fnv1a(source);
     for (gmmvi_custom_target* t : ctx->custom_targets)
-        if (t->hash == hash && t->autodiff == autodiff && t->source == source) { ++t->refs; *out = t; return GMMVI_OK; }
+        if (t->hash == hash && t->mode == mode && t->source == source) { ++t->refs; *out = t; return GMMVI_OK; }
     hipDeviceProp_t prop;
     GMMVI_HIP_CHECK(ctx, hipGetDeviceProperties(&prop, ctx->device));
     std::vector<char> code;
     std::string log;
-    const int rc = compile_source(source, autodiff, prop.gcnArchName, code, log);
+    const int rc = compile_source(source, mode, prop.gcnArchName, code, log);
     if (rc != GMMVI_OK) return gmmvi_fail(ctx, rc, log);
     gmmvi_custom_target* t = new gmmvi_custom_target();
-    t->hash = hash; t->source = source; t->autodiff = autodiff; t->refs = 1;
-    static const char* const names[4] = {"gmmvi_custom_staged_lp", "gmmvi_custom_staged_grad", "gmmvi_custom_direct_lp",
-                                         "gmmvi_custom_direct_grad"};
+    t->hash = hash; t->source = source; t->mode = mode; t->refs = 1;
+    static const char* const wrap_names[4] = {"gmmvi_custom_staged_lp", "gmmvi_custom_staged_grad", "gmmvi_custom_direct_lp",
+                                              "gmmvi_custom_direct_grad"};
+    static const char* const data_names[6] = {"gmmvi_data_rows_staged_lp", "gmmvi_data_rows_staged_grad", "gmmvi_data_rows_direct_lp",
+                                              "gmmvi_data_rows_direct_grad", "gmmvi_data_merge_lp", "gmmvi_data_merge_grad"};
+    const char* const* names = mode == MODE_DATA ? data_names : wrap_names;
+    const int count = mode == MODE_DATA ? 6 : 4;
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipModuleLoadData(&t->module, code.data());
-    for (int i = 0; e == hipSuccess && i < 4; ++i) e = hipModuleGetFunction(&t->fn[i], t->module, names[i]);
+    for (int i = 0; e == hipSuccess && i < count; ++i) e = hipModuleGetFunction(&t->fn[i], t->module, names[i]);
     if (e != hipSuccess) {
         if (t->module) (void)hipModuleUnload(t->module);
         delete t;
@@ -186,11 +211,15 @@ static int compile_target(gmmvi_ctx* ctx, const char* source, bool autodiff, gmm
 }
 
 extern "C" int gmmvi_custom_target_compile(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
-    return compile_target(ctx, source, false, out);
+    return compile_target(ctx, source, MODE_HAND, out);
 }
 
 extern "C" int gmmvi_custom_target_compile_autodiff(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
-    return compile_target(ctx, source, true, out);
+    return compile_target(ctx, source, MODE_AUTODIFF, out);
+}
+
+extern "C" int gmmvi_custom_target_compile_data(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
+    return compile_target(ctx, source, MODE_DATA, out);
 }
 
 extern "C" int gmmvi_custom_target_release(gmmvi_ctx* ctx, gmmvi_custom_target* t) {
@@ -214,10 +243,13 @@ extern "C" int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* t,
     GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
     GMMVI_ARG_CHECK(ctx, N >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && X_dev != nullptr && lp_out_dev != nullptr);
     GMMVI_ARG_CHECK(ctx, route >= 0 && route <= 2);
+    if (t->mode == MODE_DATA)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target was compiled by gmmvi_custom_target_compile_data (a row "
+                                              "term and a prior, no gmmvi_user_target): gmmvi_target_custom_data launches it");
     if (route == 1 && D > GMMVI_CUSTOM_STAGED_MAX_DIM)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: route 1 (staged) needs D <= " +
                                                   std::to_string(GMMVI_CUSTOM_STAGED_MAX_DIM) + ", got D = " + std::to_string(D));
-    if (t->autodiff && grad_out_dev != nullptr && D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM)
+    if (t->mode == MODE_AUTODIFF && grad_out_dev != nullptr && D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the gradient of a differentiated target needs D <= " +
                                                   std::to_string(GMMVI_CUSTOM_AUTODIFF_MAX_DIM) + ", got D = " + std::to_string(D) +
                                                   " (values only, or a hand-written gradient, run above)");
@@ -231,5 +263,108 @@ extern "C" int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* t,
     GMMVI_PROF(ctx, staged ? "target_custom_staged" : "target_custom_direct");
     GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[(staged ? 0 : 2) + (want_grad ? 1 : 0)], (unsigned)blocks, 1, 1, threads, 1, 1,
                                                (unsigned)lds, ctx->stream, args, nullptr));
+    return GMMVI_OK;
+}
+
+// ---- targets summed over a data set ----------------------------------------------------------------------------------------
+// The launch plan.  Auto: the row list is cut into enough chunks that ceil(N / 64) * chunks workgroups reach GMMVI_DATA_PLAN_CUS
+// (the compute units of an MI355X: one workgroup of four waves each), but into no more than rows / GMMVI_DATA_MIN_CHUNK_ROWS, so
+// that every wave of a chunk has at least GMMVI_DATA_MIN_CHUNK_ROWS / 4 rows to pay for the chunk's merge traffic and launch
+// tail.  A request is honoured up to one row per chunk.  Either way the chunks are then as even as whole rows allow, and the
+// count is what that row count per chunk needs: the last chunk is never empty.
+constexpr int GMMVI_DATA_PLAN_CUS = 256;
+constexpr int GMMVI_DATA_MIN_CHUNK_ROWS = 32;
+constexpr int64_t GMMVI_DATA_MAX_CHUNKS = 65535;           // gridDim.y
+
+extern "C" int gmmvi_custom_data_plan(int N, int64_t rows, int chunks_requested, int* chunks, int* rows_per_chunk) {
+    if (N < 1 || rows < 1 || rows > 2147483647ll || chunks_requested < 0 || !chunks || !rows_per_chunk)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_data_plan needs N >= 1, 1 <= rows < 2^31, "
+                                                  "chunks_requested >= 0 and two outputs");
+    int64_t want = chunks_requested;
+    if (want == 0) {
+        const int64_t tiles = ((int64_t)N + 63) / 64;
+        const int64_t fill = (GMMVI_DATA_PLAN_CUS + tiles - 1) / tiles;
+        const int64_t most = rows / GMMVI_DATA_MIN_CHUNK_ROWS;
+        want = fill < most ? fill : most;
+    }
+    if (want > rows) want = rows;
+    if (want > GMMVI_DATA_MAX_CHUNKS) want = GMMVI_DATA_MAX_CHUNKS;
+    if (want < 1) want = 1;
+    const int64_t per = (rows + want - 1) / want;
+    *rows_per_chunk = (int)per;
+    *chunks = (int)((rows + per - 1) / per);
+    return GMMVI_OK;
+}
+
+namespace {
+struct RowList {                 // gmmvi_data::RowList of custom_target_data.inc, member for member
+    int C;
+    unsigned T;
+    int minibatch;
+    unsigned length;
+    unsigned rows_per_chunk;
+    unsigned call, hbits, k0, k1;
+};
+static_assert(sizeof(RowList) == 36, "RowList is a kernel argument: its layout is the device text's");
+}  // namespace
+
+extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                        const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
+                                        uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                        int chunks_requested) {
+    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
+    GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
+    if (t->mode != MODE_DATA)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_data needs a target compiled by "
+                                              "gmmvi_custom_target_compile_data; gmmvi_target_custom launches the other two kinds");
+    GMMVI_ARG_CHECK(ctx, N >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && X_dev != nullptr && lp_out_dev != nullptr);
+    GMMVI_ARG_CHECK(ctx, data_dev != nullptr && (minibatch == 0 || minibatch == 1) && chunks_requested >= 0);
+    if (T < 1 || T > 2147483647ll)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the data set needs 1 <= T < 2^31 rows, got T = " + std::to_string(T));
+    if (C < 1)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: a data row needs C >= 1 floats, got C = " + std::to_string(C));
+    if (B < 1 || B > T)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the batch size needs 1 <= B <= T = " + std::to_string(T) +
+                                                  ", got B = " + std::to_string(B) + " (pass B = T with the full-data mode)");
+    const bool want_grad = grad_out_dev != nullptr;
+    if (want_grad && D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the gradient of a differentiated target needs D <= " +
+                                                  std::to_string(GMMVI_CUSTOM_AUTODIFF_MAX_DIM) + ", got D = " + std::to_string(D) +
+                                                  " (a value call runs above)");
+    const int64_t length = minibatch ? B : T;
+    int chunks = 0, rows_per_chunk = 0;
+    if (gmmvi_custom_data_plan(N, length, chunks_requested, &chunks, &rows_per_chunk) != GMMVI_OK)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_data_plan refused N, the row count or the chunk request");
+    const bool staged = D <= GMMVI_CUSTOM_STAGED_MAX_DIM;
+    const size_t tiles = ((size_t)N + 63) / 64;
+    GMMVI_ARG_CHECK(ctx, tiles <= 2147483647u);
+    float* part_lp = nullptr;
+    float* part_grad = nullptr;
+    if (chunks > 1) {
+        const size_t f_lp = (size_t)chunks * (size_t)N;
+        const int rc = gmmvi_ws_reserve(ctx, f_lp * (want_grad ? (size_t)D + 1 : 1) * sizeof(float));
+        if (rc != GMMVI_OK) return rc;
+        part_lp = (float*)ctx->ws;
+        part_grad = want_grad ? part_lp + f_lp : nullptr;
+    }
+    RowList l{C, (unsigned)T, minibatch, (unsigned)length, (unsigned)rows_per_chunk, call,
+              gmmvi_feistel_half_bits((uint32_t)T), (unsigned)seed, (unsigned)(seed >> 32)};
+    float scale = minibatch ? (float)T / (float)B : 1.f;
+    // LDS: the waves' accumulators [3][1 or 1 + W][64], then the staged x image [64][D | 1]: 13056 + 30976 B at D = 120
+    const size_t lds = ((size_t)3 * (want_grad ? 1 + GMMVI_CUSTOM_AUTODIFF_TANGENTS : 1) * 64 + (staged ? (size_t)64 * (D | 1) : 0)) *
+                       sizeof(float);
+    {
+        void* args[] = {&D, &params_dev, &X_dev, &N, &data_dev, &l, &scale, &lp_out_dev, &grad_out_dev, &part_lp, &part_grad};
+        GMMVI_PROF(ctx, "target_custom_data");
+        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[(staged ? 0 : 2) + (want_grad ? 1 : 0)], (unsigned)tiles, (unsigned)chunks, 1,
+                                                   256, 1, 1, (unsigned)lds, ctx->stream, args, nullptr));
+    }
+    if (chunks > 1) {
+        const size_t blocks = ((size_t)N + 255) / 256;
+        void* args[] = {&D, &params_dev, &X_dev, &N, &chunks, &scale, &lp_out_dev, &grad_out_dev, &part_lp, &part_grad};
+        GMMVI_PROF(ctx, "target_custom_data_merge");
+        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[4 + (want_grad ? 1 : 0)], (unsigned)blocks, 1, 1, 256, 1, 1, 0, ctx->stream,
+                                                   args, nullptr));
+    }
     return GMMVI_OK;
 }

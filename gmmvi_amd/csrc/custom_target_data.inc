@@ -1,0 +1,205 @@
+R"GMMVI_DATA(
+// ---- kernels of a user-defined target summed over a data set (csrc/custom_target.hip puts this text behind the user's source,
+// the dual-number text, the tile mover of custom_target_wrap.inc and the Feistel stream of feistel.h; contract:
+// include/gmmvi_hip.h, "user-defined targets summed over a data set") ------------------------------------------------------------
+// The text above defines
+//     template <class T, class X> __device__ T gmmvi_user_row  (X x, int D, const float* row, int C, const float* params);
+//     template <class T, class X> __device__ T gmmvi_user_prior(X x, int D, const float* params);
+// and the target is  lp(x) = prior(x) + s * sum over the row list of row(x, data[r]).
+//
+// gmmvi_data_rows_*: grid (ceil(N / 64), chunks), 256 threads = 4 waves on the same 64 consecutive samples, lane = sample in
+// every wave.  A workgroup owns rows_per_chunk consecutive positions of the row list; its wave w takes positions w, w + 4, ...
+// of them.  Wave id, position and row index are wave-uniform by construction (readfirstlane), so a minibatch costs one Feistel
+// walk per wave and row, and the row's floats come through uniform loads.
+// Summation order (fixed, no atomics): within a wave in position order; wave 0 adds waves 1, 2, 3 in that order (LDS); chunks
+// in index order (gmmvi_data_merge_*, or not at all with one chunk); then  s * sum,  then  + prior.
+// params, X and the data set are __restrict__ kernel arguments: nothing a kernel stores can change them, which is what lets the
+// compiler keep the uniform loads of a row on the scalar path although the passes of a gradient call store in between.
+// LDS: [3][1 or 1 + W][64] wave accumulators, then (staged) the x image [64][D | 1].
+
+namespace gmmvi_data {
+
+using gmmvi_ad::Dual;
+using gmmvi_ad::Seed;
+constexpr int W = gmmvi_ad::W;
+
+struct RowList {                // of the data set data[T, C]
+    int C;
+    unsigned T;
+    int minibatch;              // 0: position p is row p; 1: row pi(p) of the stream of (seed, call)
+    unsigned length;            // T, or the batch size
+    unsigned rows_per_chunk;
+    unsigned call, hbits, k0, k1;
+};
+
+__device__ __forceinline__ const float* row_at(const float* data, const RowList& l, unsigned p) {
+    unsigned r = p;
+    if (l.minibatch) r = gmmvi_feistel_permute(p, 0u, l.call, GMMVI_STREAM_DATA_MINIBATCH, l.T, l.hbits, l.k0, l.k1);
+    r = (unsigned)__builtin_amdgcn_readfirstlane((int)r);
+    return data + (size_t)r * (size_t)l.C;
+}
+
+// wave 0 receives the sum of the four waves' `count` floats per lane, added in the order 0, 1, 2, 3; two barriers
+template <int COUNT>
+__device__ __forceinline__ void merge_waves(float (&acc)[COUNT], float* red, int w, int lane) {
+    if (w > 0) {
+#pragma unroll
+        for (int k = 0; k < COUNT; ++k) red[((w - 1) * COUNT + k) * 64 + lane] = acc[k];
+    }
+    __syncthreads();
+    if (w == 0) {
+#pragma unroll
+        for (int v = 0; v < 3; ++v) {
+#pragma unroll
+            for (int k = 0; k < COUNT; ++k) acc[k] += red[(v * COUNT + k) * 64 + lane];
+        }
+    }
+    __syncthreads();
+}
+
+// s * sum + prior for one pass (GRAD) or the value: what the last stage of either kernel does with a merged row sum
+__device__ __forceinline__ float finish_value(float sum, float scale, const float* x, int D, const float* params) {
+    const float scaled = scale * sum;
+    return scaled + gmmvi_user_prior<float, const float*>(x, D, params);
+}
+__device__ __forceinline__ Dual finish_pass(const Dual& sum, float scale, const float* x, int first, int D, const float* params) {
+    const Dual scaled = scale * sum;
+    return scaled + gmmvi_user_prior<Dual, Seed>(Seed{x, first}, D, params);
+}
+
+template <bool GRAD, bool STAGED>
+__device__ __forceinline__ void rows(int D, const float* params, const float* X, int N, const float* data, RowList l, float scale,
+                                     float* lp, float* grad, float* part_lp, float* part_grad) {
+    extern __shared__ float gmmvi_data_lds[];
+    constexpr int COUNT = GRAD ? 1 + W : 1;
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int S = D | 1;
+    const size_t n0 = (size_t)blockIdx.x * 64;
+    const int valid = (size_t)N - n0 < 64 ? (int)((size_t)N - n0) : 64;
+    const int mine = lane < valid ? lane : valid - 1;     // lanes past N recompute the tile's last sample and write nothing
+    float* red = gmmvi_data_lds;
+    float* xs = gmmvi_data_lds + 3 * COUNT * 64;
+    const float* x;
+    if (STAGED) {
+        const int r0 = 16 * w;                            // wave w moves rows 16 w .. 16 w + 15 of the tile
+        const int count = valid - r0 < 16 ? valid - r0 : 16;
+        if (count > 0)
+            gmmvi_wrap::move_tile<true>(const_cast<float*>(X) + (n0 + r0) * (size_t)D, xs + r0 * S, D, S, count * D, lane);
+        __syncthreads();
+        x = xs + mine * S;
+    } else {
+        x = X + (n0 + mine) * (size_t)D;
+    }
+    const unsigned chunk = blockIdx.y;
+    const bool single = gridDim.y == 1;
+    const unsigned begin = chunk * l.rows_per_chunk;
+    const unsigned end = l.length - begin < l.rows_per_chunk ? l.length : begin + l.rows_per_chunk;
+    const size_t n = n0 + lane;
+    const size_t slot = (size_t)chunk * (size_t)N + n;    // of the partials
+
+    if constexpr (!GRAD) {
+        float acc[1] = {0.f};
+        for (unsigned p = begin + w; p < end; p += 4)
+            acc[0] += gmmvi_user_row<float, const float*>(x, D, row_at(data, l, p), l.C, params);
+        merge_waves<1>(acc, red, w, lane);
+        if (w == 0) {
+            if (single) {
+                const float v = finish_value(acc[0], scale, x, D, params);
+                if (lane < valid) lp[n] = v;
+            } else if (lane < valid) {
+                part_lp[slot] = acc[0];
+            }
+        }
+    } else {
+        for (int first = 0; first < D; first += W) {
+            Dual sum(0.f);
+            for (unsigned p = begin + w; p < end; p += 4)
+                sum += gmmvi_user_row<Dual, Seed>(Seed{x, first}, D, row_at(data, l, p), l.C, params);
+            float acc[COUNT];
+            acc[0] = sum.v;
+#pragma unroll
+            for (int j = 0; j < W; ++j) acc[1 + j] = sum.d[j];
+            merge_waves<COUNT>(acc, red, w, lane);
+            if (w == 0) {
+                sum.v = acc[0];
+#pragma unroll
+                for (int j = 0; j < W; ++j) sum.d[j] = acc[1 + j];
+                if (single) {
+                    const Dual t = finish_pass(sum, scale, x, first, D, params);
+                    if (lane < valid) {
+                        if (first == 0) lp[n] = t.v;
+#pragma unroll
+                        for (int j = 0; j < W; ++j)
+                            if (first + j < D) grad[n * (size_t)D + first + j] = t.d[j];
+                    }
+                } else if (lane < valid) {
+                    if (first == 0) part_lp[slot] = sum.v;
+#pragma unroll
+                    for (int j = 0; j < W; ++j)
+                        if (first + j < D) part_grad[slot * (size_t)D + first + j] = sum.d[j];
+                }
+            }
+        }
+    }
+}
+
+// chunks > 1: the thread is the sample; adds the chunks' partials in index order, then s * sum + prior
+template <bool GRAD>
+__device__ __forceinline__ void merge(int D, const float* params, const float* X, int N, int chunks, float scale, float* lp,
+                                      float* grad, const float* part_lp, const float* part_grad) {
+    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= (size_t)N) return;
+    const float* x = X + n * (size_t)D;
+    float value = 0.f;
+    for (int c = 0; c < chunks; ++c) value += part_lp[(size_t)c * (size_t)N + n];
+    if constexpr (!GRAD) {
+        lp[n] = finish_value(value, scale, x, D, params);
+    } else {
+        for (int first = 0; first < D; first += W) {
+            Dual sum(0.f);
+            sum.v = value;
+            for (int c = 0; c < chunks; ++c) {
+                const float* g = part_grad + ((size_t)c * (size_t)N + n) * (size_t)D + first;
+#pragma unroll
+                for (int j = 0; j < W; ++j)
+                    if (first + j < D) sum.d[j] += g[j];
+            }
+            const Dual t = finish_pass(sum, scale, x, first, D, params);
+            if (first == 0) lp[n] = t.v;
+#pragma unroll
+            for (int j = 0; j < W; ++j)
+                if (first + j < D) grad[n * (size_t)D + first + j] = t.d[j];
+        }
+    }
+}
+
+}  // namespace gmmvi_data
+
+#define GMMVI_DATA_ROWS_KERNEL(name, GRAD, STAGED)                                                                          \
+    extern "C" __global__ __launch_bounds__(256) void name(int D, const float* __restrict__ params,                         \
+                                                           const float* __restrict__ X, int N,                             \
+                                                           const float* __restrict__ data, gmmvi_data::RowList l,          \
+                                                           float scale, float* lp, float* grad, float* part_lp,            \
+                                                           float* part_grad) {                                             \
+        gmmvi_data::rows<GRAD, STAGED>(D, params, X, N, data, l, scale, lp, grad, part_lp, part_grad);                     \
+    }
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_staged_lp, false, true)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_staged_grad, true, true)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_direct_lp, false, false)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_direct_grad, true, false)
+#undef GMMVI_DATA_ROWS_KERNEL
+
+extern "C" __global__ __launch_bounds__(256) void gmmvi_data_merge_lp(int D, const float* __restrict__ params,
+                                                                       const float* __restrict__ X, int N, int chunks, float scale,
+                                                                       float* lp, float* grad, const float* part_lp,
+                                                                       const float* part_grad) {
+    gmmvi_data::merge<false>(D, params, X, N, chunks, scale, lp, grad, part_lp, part_grad);
+}
+extern "C" __global__ __launch_bounds__(256) void gmmvi_data_merge_grad(int D, const float* __restrict__ params,
+                                                                         const float* __restrict__ X, int N, int chunks, float scale,
+                                                                         float* lp, float* grad, const float* part_lp,
+                                                                         const float* part_grad) {
+    gmmvi_data::merge<true>(D, params, X, N, chunks, scale, lp, grad, part_lp, part_grad);
+}
+)GMMVI_DATA"

@@ -2,7 +2,8 @@ R"GMMVI_WRAP(
 // ---- wrapper kernels of a user-defined target (csrc/custom_target.hip appends this text to the user's source) -------------
 // The text above defines   __device__ float gmmvi_user_target(const float* x, int D, const float* params, float* grad);
 // (contract: include/gmmvi_hip.h).  Each kernel below has exactly one call site of it, so that it is inlined and the address
-// space of the row pointers follows from the call.
+// space of the row pointers follows from the call.  With GMMVI_WRAP_TILE_ONLY the text stops behind move_tile: the kernels of
+// custom_target_data.inc use the tile mover and have no gmmvi_user_target to call.
 
 namespace gmmvi_wrap {
 
@@ -44,6 +45,7 @@ __device__ __forceinline__ void move_tile(float* g, float* image, int D, int S, 
     }
 }
 
+#ifndef GMMVI_WRAP_TILE_ONLY
 // Staged route: one wavefront per workgroup, 64 consecutive samples.  LDS: x image [64][D | 1], then (GRAD) the gradient
 // image of the same shape.  Rows past N are neither read nor written.
 template <bool GRAD>
@@ -76,8 +78,10 @@ __device__ __forceinline__ void direct(int D, const float* params, const float* 
     lp[n] = v;
 }
 
+#endif
 }  // namespace gmmvi_wrap
 
+#ifndef GMMVI_WRAP_TILE_ONLY
 extern "C" __global__ __launch_bounds__(64) void gmmvi_custom_staged_lp(int D, const float* params, const float* X, int N,
                                                                          float* lp, float* grad) {
     gmmvi_wrap::staged<false>(D, params, X, N, lp, grad);
@@ -94,4 +98,5 @@ extern "C" __global__ __launch_bounds__(256) void gmmvi_custom_direct_grad(int D
                                                                             float* lp, float* grad) {
     gmmvi_wrap::direct<true>(D, params, X, N, lp, grad);
 }
+#endif
 )GMMVI_WRAP"

@@ -1,13 +1,14 @@
 // Row permutation of the minibatch streams: pi(r) is a balanced 4-round Feistel network on 2h bits
 // (h = ceil(ceil(log2 T) / 2)) walked until it lands in [0, T) (cycle walking); round i maps (L, R) -> (R, L xor
 // (F_i(R) & (2^h - 1))) with F_i(R) = word 0 of Philox4x32-10 (philox.h), key (k0, k1) and counter
-// (R | i << 24, epoch, call, stream).  Stream ids 0-2 are the samplers of oracle/philox.py; the two below are the
+// (R | i << 24, epoch, call, stream).  Stream ids 0-2 are the samplers of oracle/philox.py; the three below are the
 // minibatch streams.  experiments/target_distributions/minibatch_stream.py restates all of this in NumPy.
 #pragma once
 #include "philox.h"
 
 constexpr uint32_t GMMVI_STREAM_BNN_MINIBATCH = 3;       // bnn.hip, bnn_classifier.hip, bnn_mlp.hip
 constexpr uint32_t GMMVI_STREAM_LOGREG_MINIBATCH = 4;    // logreg_mb.hip: epoch word 0, its own position rule
+constexpr uint32_t GMMVI_STREAM_DATA_MINIBATCH = 5;      // custom_target_data.inc: epoch word 0, batch row j is pi(j)
 
 // h for a permutation of [0, T)
 __host__ __device__ inline uint32_t gmmvi_feistel_half_bits(uint32_t T) {

@@ -15,12 +15,21 @@ iteration take it as target kind 5.
 
 and the library differentiates it in forward mode (csrc/custom_target_autodiff.inc): upstream's "write log_density, the framework
 differentiates it" (SampleSelector.get_target_grads) on the device.
+
+``DeviceDataLNPDF`` takes one data row's log-likelihood and the prior,
+
+    template <class T, class X> __device__ T gmmvi_user_row  (X x, int D, const float* row, int C, const float* params);
+    template <class T, class X> __device__ T gmmvi_user_prior(X x, int D, const float* params);
+
+and the library spreads the rows over waves and workgroups, differentiates, sums in a fixed order and can draw a minibatch per
+call (csrc/custom_target_data.inc): log p(x) = log prior(x) + sum_r log p(data_r | x) without a hand-written kernel file.
 """
 import numpy as np
 
 from ... import _lib, hip_ops
 from ...device import get_context
 from .lnpdf import LNPDF
+from .minibatch_stream import MinibatchLNPDF
 
 
 class DeviceLNPDF(LNPDF):
@@ -104,3 +113,67 @@ class DeviceAutodiffLNPDF(_DeviceLNPDFWithGradient):
 
     def _compile(self):
         return hip_ops.custom_target_compile(self.ctx, self.source, autodiff=True)
+
+
+class DeviceDataLNPDF(MinibatchLNPDF):
+    """``DeviceDataLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0)``: ``source`` defines
+    ``gmmvi_user_row`` and ``gmmvi_user_prior`` (contract: include/gmmvi_hip.h), ``data`` is the 2-D data set, uploaded once as
+    fp32, and the target is ``prior(x) + s * sum_r row(x, data[r])``.
+
+    batch_size=None: all rows in index order, s = 1.  A batch size B: every evaluation draws the B rows of
+    ``minibatch_stream.data_minibatch_rows(seed, call_count, B, T)``, one batch shared by all samples, with s = T / B, and
+    ``call_count`` advances after each evaluation that receives at least one sample (the protocol of ``MinibatchLNPDF``);
+    ``log_density_full(x)`` is then the full-data value in index order, counter untouched.
+    The gradient comes from the library's dual numbers (num_dimensions <= _lib.CUSTOM_AUTODIFF_MAX_DIM) and is computed only
+    for an estimator that reads it.  There is no ``_fast_path_target``: the iteration runs module by module, as for the other
+    minibatch targets."""
+
+    gradient_on_demand = True
+
+    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0):
+        super().__init__(seed)
+        if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
+            raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
+        if int(num_dimensions) > _lib.CUSTOM_AUTODIFF_MAX_DIM:
+            raise ValueError(f"num_dimensions must be <= {_lib.CUSTOM_AUTODIFF_MAX_DIM} for a differentiated target, got "
+                             f"{num_dimensions}: the gradient costs ceil(D / {_lib.CUSTOM_AUTODIFF_TANGENTS}) passes per sample "
+                             "and row")
+        data = np.ascontiguousarray(np.asarray(data.numpy() if hasattr(data, "numpy") else data), np.float32)
+        if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] < 1:
+            raise ValueError(f"data must be two-dimensional [rows >= 1, floats per row >= 1], got shape {data.shape}")
+        if batch_size is not None and (int(batch_size) != batch_size or not 1 <= int(batch_size) <= data.shape[0]):
+            raise ValueError(f"batch_size must be an integer in 1..{data.shape[0]} (the rows of data) or None, got {batch_size!r}")
+        if params is not None:
+            params = np.ascontiguousarray(np.asarray(params.numpy() if hasattr(params, "numpy") else params), np.float32)
+            if params.ndim != 1:
+                raise ValueError(f"params must be one-dimensional, got shape {params.shape}")
+        self.ctx = get_context()
+        self.source = str(source)
+        self.batch_size = None if batch_size is None else int(batch_size)
+        self.num_data = int(data.shape[0])
+        self._num_dimensions = int(num_dimensions)
+        self._data_dev = self.ctx.asarray(data)
+        self._params_dev = None if params is None or params.size == 0 else self.ctx.asarray(params)
+        self._handle = hip_ops.custom_target_compile(self.ctx, self.source, mode="data")
+
+    def get_num_dimensions(self):
+        return self._num_dimensions
+
+    def _x(self, x):
+        x = self.ctx.asarray(x)
+        if len(x.shape) != 2 or x.shape[1] != self._num_dimensions:
+            raise ValueError(f"samples: expected [n, {self._num_dimensions}], got {x.shape}")
+        return x
+
+    def _launch(self, x, call, want_grad):
+        return hip_ops.target_custom_data(self.ctx, self._handle, self._params_dev, self._data_dev, self._x(x), want_grad=want_grad,
+                                          batch_size=self.batch_size, seed=self.seed, call=call)
+
+    def _evaluate(self, x, want_grad):
+        if self.batch_size is None:                       # no stream, no counter
+            return self._launch(self.ctx.asarray(x), 0, want_grad)
+        return super()._evaluate(x, want_grad)
+
+    def log_density_full(self, x):
+        """The full-data log density (all rows in index order, s = 1) of a minibatch target; the call counter stays."""
+        return hip_ops.target_custom_data(self.ctx, self._handle, self._params_dev, self._data_dev, self._x(x), want_grad=False)[0]

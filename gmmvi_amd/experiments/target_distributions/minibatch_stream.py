@@ -5,13 +5,14 @@ A stream permutes the T training rows by pi_{seed,call,epoch}, a balanced 4-roun
 (h = ceil(ceil(log2 T) / 2)) with cycle walking, round i mapping (L, R) -> (R, L xor (F_i(R) & (2^h - 1))), F_i(R) = word 0
 of Philox4x32-10 with key (seed lo, seed hi) and counter (R | i << 24, epoch, call, stream).  Stream ids 0-2 are the
 samplers (component normals, categorical draws, mixture normals); 3 is the Bayesian neural networks' stream
-(``minibatch_rows`` below), 4 the minibatch logistic regressions' (epoch word 0, ``logistic_regression.minibatch_rows``).
+(``minibatch_rows`` below), 4 the minibatch logistic regressions' (epoch word 0, ``logistic_regression.minibatch_rows``), 5
+the minibatches of user-defined targets summed over a data set (epoch word 0, ``data_minibatch_rows`` below).
 """
 import numpy as np
 
 from .lnpdf import LNPDF
 
-STREAM_BNN_MINIBATCH, STREAM_LOGREG_MINIBATCH = 3, 4
+STREAM_BNN_MINIBATCH, STREAM_LOGREG_MINIBATCH, STREAM_DATA_MINIBATCH = 3, 4, 5
 
 _M0, _M1 = np.uint64(0xD2511F53), np.uint64(0xCD9E8D57)
 _W0, _W1 = 0x9E3779B9, 0xBB67AE85
@@ -64,6 +65,15 @@ def minibatch_rows(seed, call, n, batch_size, num_data):
     position p = i * batch_size + j, epoch p div T and rank p mod T: every epoch visits every row once."""
     p = np.arange(int(n) * int(batch_size), dtype=np.int64)
     return permute_rows(seed, call, p // num_data, p % num_data, num_data).reshape(int(n), int(batch_size))
+
+
+def data_minibatch_rows(seed, call, batch_size, num_data):
+    """The data rows of the minibatch of call ``call`` of a ``DeviceDataLNPDF``: int64 [batch_size], row j = pi(j) of epoch 0 on
+    stream 5.  One batch per call, shared by all samples; batch_size == num_data is a permutation of all rows."""
+    if not 1 <= int(batch_size) <= int(num_data):
+        raise ValueError(f"batch_size must be in 1..{num_data}, got {batch_size}")
+    j = np.arange(int(batch_size), dtype=np.int64)
+    return permute_rows(seed, call, np.zeros_like(j), j, num_data, stream=STREAM_DATA_MINIBATCH)
 
 
 class MinibatchLNPDF(LNPDF):

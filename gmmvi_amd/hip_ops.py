@@ -110,6 +110,25 @@ def custom_target_check_autodiff(source, arch="gfx950"):
     return int(rc), log.value.decode(errors="replace")
 
 
+def custom_target_check_data(source, arch="gfx950"):
+    """custom_target_check for a source that defines ``gmmvi_user_row`` and ``gmmvi_user_prior`` (a target summed over a data set,
+    csrc/custom_target_data.inc).  -> (status, compiler log)."""
+    import ctypes as C
+    log = C.create_string_buffer(1 << 16)
+    rc = _lib.load().gmmvi_custom_target_check_data(str(source).encode(), str(arch).encode(), log, len(log))
+    return int(rc), log.value.decode(errors="replace")
+
+
+def custom_data_plan(n, rows, chunks_requested=0):
+    """The launch plan of ``target_custom_data`` for n samples and a row list of ``rows`` (gmmvi_custom_data_plan; needs no
+    device) -> (chunks, rows_per_chunk)."""
+    import ctypes as C
+    chunks, per = C.c_int(), C.c_int()
+    lib = _lib.load()
+    _lib.check(None, lib.gmmvi_custom_data_plan(int(n), int(rows), int(chunks_requested), C.byref(chunks), C.byref(per)))
+    return chunks.value, per.value
+
+
 class CustomTarget:
     """A compiled user target of a context (gmmvi_custom_target); released with the object."""
 
@@ -129,13 +148,22 @@ class CustomTarget:
             pass
 
 
-def custom_target_compile(ctx, source, autodiff=False):
-    """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  autodiff: the source
-    defines ``gmmvi_user_density`` and the library differentiates it.  A source that does not compile raises GmmviError with
-    the compiler log."""
+CUSTOM_TARGET_MODES = ("hand", "autodiff", "data")
+
+
+def custom_target_compile(ctx, source, autodiff=False, mode=None):
+    """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  mode: "hand" (the
+    source defines ``gmmvi_user_target``), "autodiff" (``gmmvi_user_density``, the library differentiates it) or "data"
+    (``gmmvi_user_row`` and ``gmmvi_user_prior``, launched by ``target_custom_data``); None: ``autodiff`` chooses between the
+    first two.  A source that does not compile raises GmmviError with the compiler log."""
     import ctypes as C
+    if mode is None:
+        mode = "autodiff" if autodiff else "hand"
+    if mode not in CUSTOM_TARGET_MODES:
+        raise ValueError(f"mode: expected one of {CUSTOM_TARGET_MODES}, got {mode!r}")
     h = C.c_void_p()
-    compile_fn = ctx.lib.gmmvi_custom_target_compile_autodiff if autodiff else ctx.lib.gmmvi_custom_target_compile
+    compile_fn = {"hand": ctx.lib.gmmvi_custom_target_compile, "autodiff": ctx.lib.gmmvi_custom_target_compile_autodiff,
+                  "data": ctx.lib.gmmvi_custom_target_compile_data}[mode]
     ctx.check(compile_fn(ctx.handle, str(source).encode(), C.byref(h)))
     return CustomTarget(ctx, h)
 
@@ -156,6 +184,33 @@ def target_custom(ctx, handle, params, x, want_grad=True, route=0):
     if n > 0:
         ctx.check(ctx.lib.gmmvi_target_custom(ctx.handle, handle.handle, d, None if params is None else params.ptr, x.ptr, n,
                                               lp.ptr, None if grad is None else grad.ptr, int(route)))
+    return lp, grad
+
+
+def target_custom_data(ctx, handle, params, data, x, want_grad=True, batch_size=None, seed=0, call=0, chunks=0):
+    """Data-mode user target ``handle`` on x [n, D]: prior(x) + s * sum of the row terms over data [T, C]
+    (csrc/custom_target_data.inc).  batch_size None: all rows in index order, s = 1; a number: the minibatch of (seed, call)
+    with s = T / batch_size.  chunks: 0 lets the library plan the launch, a positive number forces that many row chunks.
+    -> (lp [n], grad [n, D] or None)."""
+    if not isinstance(handle, CustomTarget):
+        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
+    n, d = x.shape
+    _req(x, (n, d), name="x")
+    if len(data.shape) != 2:
+        raise ValueError(f"data: expected a two-dimensional array, got {data.shape}")
+    t, c = data.shape
+    _req(data, (t, c), name="data")
+    if params is not None:
+        if len(params.shape) != 1:
+            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
+        _req(params, params.shape, name="params")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_custom_data(
+            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c,
+            0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks)))
     return lp, grad
 
 

@@ -344,8 +344,8 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  * The library puts its dual-number text (csrc/custom_target_autodiff.inc) and then the wrapper kernels behind the source; the
  * source stays first, so the compiler's line numbers are the user's, and the overloads are found by argument-dependent lookup
  * when the template is instantiated (one declaration, gmmvi_value(float), goes in front of the source's first line, on that
- * line: a float has no namespace for that lookup).  In this mode, and in no other, the compiler is also given
- * -DGMMVI_CUSTOM_AUTODIFF_TANGENTS=<W>, so a text can tell the modes apart.  On a T the text defines
+ * line: a float has no namespace for that lookup).  In this mode and in the data mode below, not in the hand-written one, the
+ * compiler is also given -DGMMVI_CUSTOM_AUTODIFF_TANGENTS=<W>, so a text can tell the modes apart.  On a T the text defines
  *   - + - * / and += -= *= /= between T and T, T and float, float and T; unary minus;
  *   - < <= > >= == !=, decided on the values;
  *   - exp expm1 log log1p sqrt rsqrt sin cos tan tanh atan fabs fmax fmin, pow(T, float) and pow(T, T), each also under its
@@ -372,6 +372,58 @@ int gmmvi_custom_target_compile_autodiff(gmmvi_ctx* ctx, const char* source, gmm
  * operations in the order of csrc/autodiff_probe.hip (gmmvi_amd/_lib.py AUTODIFF_OPS names them); comparisons give 1 or 0
  * with tangent 0.  An unknown op or a NULL output: GMMVI_ERR_ARG. */
 int gmmvi_autodiff_probe(int op, float a, float da, float b, float db, float* value, float* tangent);
+
+/* ---- user-defined targets summed over a data set --------------------------------------------------------------------------------
+ * Posteriors of the shape  log p(x) = log prior(x) + sum over the data rows r of log p(data_r | x):  the source defines one
+ * row's term and the prior, value-only templates under the purity rules and with the operations of gmmvi_user_density above,
+ *
+ *     template <class T, class X> __device__ T gmmvi_user_row  (X x, int D, const float* row, int C, const float* params);
+ *     template <class T, class X> __device__ T gmmvi_user_prior(X x, int D, const float* params);
+ *
+ *   - row: the C floats of one data row (plain float, never differentiated); params: the target's own device array, or NULL;
+ *   - the text may not define names that begin with gmmvi_ other than these two (and gmmvi_user_density / gmmvi_user_target
+ *     behind a test of the mode's macros: this mode defines GMMVI_CUSTOM_AUTODIFF_TANGENTS and GMMVI_AD_NO_ADAPTER).
+ * The target is
+ *
+ *     lp(x) = prior(x) + s * sum_{r in R} row(x, data[r])
+ *
+ *   - full data (minibatch == 0): R = all T rows in index order, s = 1;
+ *   - a minibatch of B rows for (seed, call) (minibatch == 1): R = { pi(j) : 0 <= j < B } in the order of j, with
+ *     pi(j) = gmmvi_feistel_permute(j, epoch 0, call, stream 5, T, h, seed lo, seed hi) (csrc/feistel.h; NumPy:
+ *     minibatch_stream.data_minibatch_rows) and s = (float)T / (float)B.  One batch per call, shared by all samples (upstream's
+ *     use_own_batch_per_sample=False); B == T is a permuted full pass.
+ * Order of the arithmetic, all fp32: the row terms are added first (order below); s multiplies the merged row sum ONCE; the
+ * prior is added last.  The gradient is the same expression on dual numbers: s * (sum of the row tangents) + prior tangent.
+ * Kernels (csrc/custom_target_data.inc): a workgroup of 256 threads = 4 waves serves 64 consecutive samples, lane = sample in
+ * every wave; the grid is ceil(N / 64) x chunks.  A workgroup owns one contiguous chunk of rows_per_chunk positions of the row
+ * list, its wave w the positions w, w + 4, ... of the chunk; the row index (and the Feistel walk behind it) is wave-uniform, so
+ * the row's floats come through uniform loads.  x is staged in LDS up to GMMVI_CUSTOM_STAGED_MAX_DIM and read from global memory
+ * above.  A value call is one float instantiation per (sample, row); a gradient call makes ceil(D / W) passes of the dual
+ * instantiation, W = GMMVI_CUSTOM_AUTODIFF_TANGENTS, the value taken from pass 0, and is capped at GMMVI_CUSTOM_AUTODIFF_MAX_DIM.
+ * Summation order (no atomics; the same inputs and the same chunk count give the same bits): a wave adds its rows in position
+ * order; wave 0 adds the sums of waves 1, 2, 3 in that order; with more than one chunk the partials [chunks][N] and
+ * [chunks][N][D] go to the context's scratch and a second kernel adds them in chunk order.  Different chunk counts round
+ * differently: results agree within the rounding of the sum, not bitwise. */
+int gmmvi_custom_target_check_data(const char* source, const char* arch, char* log_out, size_t log_cap);
+/* A source without gmmvi_user_row or without gmmvi_user_prior: GMMVI_ERR_ARG, the log names the missing one.  The handle is an
+ * ordinary gmmvi_custom_target (released by gmmvi_custom_target_release; the mode is part of the context's key), launched by
+ * gmmvi_target_custom_data only: gmmvi_target_custom, and so target kind 5, refuse it with GMMVI_ERR_ARG. */
+int gmmvi_custom_target_compile_data(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out);
+/* The launch plan, a host function (no device, no context).  chunks_requested == 0 (auto): enough chunks that
+ * ceil(N / 64) * chunks workgroups reach 256 (one per compute unit of an MI355X), but at most rows / 32, so that every wave of
+ * a chunk has at least 8 rows; at least 1.  chunks_requested > 0 is honoured up to one row per chunk (and 65535).  Then
+ * *rows_per_chunk = ceil(rows / chunks) and *chunks = ceil(rows / *rows_per_chunk): the last chunk is never empty.  N < 1,
+ * rows outside 1 .. 2^31 - 1, a negative request or a NULL output: GMMVI_ERR_ARG. */
+int gmmvi_custom_data_plan(int N, int64_t rows, int chunks_requested, int* chunks, int* rows_per_chunk);
+/* lp[n] (and grad[n] when grad_out_dev != NULL) of the target above.  data_dev[T,C] fp32, X_dev[N,D], lp_out_dev[N],
+ * grad_out_dev[N,D] or NULL.  minibatch: 0 full data in index order, 1 the batch of (seed, call); the flag, not B, chooses.
+ * chunks_requested as for gmmvi_custom_data_plan with rows = T (full data) or B.  GMMVI_ERR_ARG before any launch, naming the
+ * limit: T outside 1 .. 2^31 - 1; C < 1; B outside 1 .. T (in either mode; pass B = T with full data); N < 1; D outside
+ * 1 .. GMMVI_MAX_DIM_DIAG; a gradient pointer with D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM (a value call runs above); a NULL data_dev,
+ * X_dev or lp_out_dev; a handle of another mode or context.  Profiling tags: target_custom_data, target_custom_data_merge. */
+int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                             const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed, uint32_t call,
+                             const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int chunks_requested);
 
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
