@@ -18,6 +18,9 @@ MAX_DIM_BLOCKED = 512          # dense [K, D, D] factors (blocked kernels) exist
 CUSTOM_STAGED_MAX_DIM = 120    # gmmvi_target_custom: the staged (LDS) route up to here, the direct route above
 CUSTOM_AUTODIFF_TANGENTS = 16  # GMMVI_CUSTOM_AUTODIFF_TANGENTS: tangents per pass of a differentiated user-defined target
 CUSTOM_AUTODIFF_MAX_DIM = 512  # gradient calls through a differentiated target stop here (the largest full-covariance D)
+CUSTOM_TAPE_RECORD_BYTES = 20       # GMMVI_CUSTOM_TAPE_RECORD_BYTES: scratch per lane and record of a tape-mode gradient call
+CUSTOM_TAPE_DEFAULT_CAPACITY = 1024 # GMMVI_CUSTOM_TAPE_DEFAULT_CAPACITY: records per lane of a handle's first gradient launch
+CUSTOM_TAPE_SCRATCH_BYTES = 1 << 31 # GMMVI_CUSTOM_TAPE_SCRATCH_BYTES: default budget of the tape scratch
 MAX_DIM_DIAG = 131072          # diagonal-covariance mixtures: csrc/diag_sweep.hip, csrc/diag.hip
 BLOCKED_ABOVE_DEFAULT = 50     # csrc/blocked.h: D > 50 runs the blocked (MFMA) kernels
 
@@ -192,6 +195,12 @@ _PROTOS = {
     "gmmvi_custom_target_compile_data": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i)]),
     "gmmvi_target_custom_data": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i]),
+    "gmmvi_custom_target_check_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
+    "gmmvi_custom_target_compile_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
+    "gmmvi_custom_tape_plan": (_i, [_i, _i, _sz, C.POINTER(_i), C.POINTER(_i)]),
+    "gmmvi_custom_tape_length": (_i, [_p, _p, _i, C.POINTER(_i)]),
+    "gmmvi_target_custom_tape": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _sz]),
+    "gmmvi_tape_probe": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),

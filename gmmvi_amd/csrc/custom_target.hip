@@ -8,6 +8,8 @@
 // gmmvi_user_prior; behind it go the dual-number text without its adapter, the tile mover of the wrapper text, the Feistel
 // stream (feistel.h and philox.h, made one string by the Makefile) and the kernels of custom_target_data.inc, which
 // gmmvi_target_custom_data launches.
+// Targets differentiated on a tape (gmmvi_custom_target_compile_tape): the source of the differentiated mode, unchanged; behind it
+// goes custom_target_tape.inc alone, the tape's number type and its two kernels, which gmmvi_target_custom_tape launches.
 #include "common.h"
 #include "feistel.h"
 #include <hip/hiprtc.h>
@@ -24,14 +26,17 @@ static const char* const kDataText =
 #include "build/feistel_text.inc"
 #include "custom_target_data.inc"
     ;
+static const char* const kTapeText =
+#include "custom_target_tape.inc"
+    ;
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
 // the float instantiation of the user's template finds gmmvi_value only if it is declared before the template.
 static const char* const kAutodiffPrelude = "__host__ __device__ inline float gmmvi_value(float); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
 
-enum Mode { MODE_HAND = 0, MODE_AUTODIFF = 1, MODE_DATA = 2 };   // what the source defines: gmmvi_user_target; gmmvi_user_density;
-                                                                 // gmmvi_user_row and gmmvi_user_prior
+// what the source defines: gmmvi_user_target; gmmvi_user_density; gmmvi_user_row and gmmvi_user_prior; gmmvi_user_density again
+enum Mode { MODE_HAND = 0, MODE_AUTODIFF = 1, MODE_DATA = 2, MODE_TAPE = 3 };
 
 namespace {
 struct Hiprtc {
@@ -82,11 +87,16 @@ const Hiprtc& hiprtc() {
 int compile_source(const char* source, Mode mode, const char* arch, std::vector<char>& code, std::string& log) {
     const Hiprtc& rt = hiprtc();
     if (!rt.why.empty()) { log = rt.why; return GMMVI_ERR_HIP; }
-    std::string text = mode == MODE_HAND ? std::string(source) : std::string(kAutodiffPrelude) + source + "\n" + kAutodiffText;
-    text += std::string("\n") + kWrapText;
-    if (mode == MODE_DATA) text += std::string("\n") + kDataText;
-    static const char* const entries[3][2] = {{"gmmvi_user_target", nullptr}, {"gmmvi_user_density", nullptr},
-                                              {"gmmvi_user_row", "gmmvi_user_prior"}};
+    std::string text = mode == MODE_HAND ? std::string(source) : std::string(kAutodiffPrelude) + source + "\n";
+    if (mode == MODE_TAPE) {
+        text += kTapeText;
+    } else {
+        if (mode != MODE_HAND) text += kAutodiffText;
+        text += std::string("\n") + kWrapText;
+        if (mode == MODE_DATA) text += std::string("\n") + kDataText;
+    }
+    static const char* const entries[4][2] = {{"gmmvi_user_target", nullptr}, {"gmmvi_user_density", nullptr},
+                                              {"gmmvi_user_row", "gmmvi_user_prior"}, {"gmmvi_user_density", nullptr}};
     hiprtcProgram prog = nullptr;
     hiprtcResult r = rt.create(&prog, text.c_str(), "gmmvi_user_target.hip", 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) { log = std::string("hiprtcCreateProgram: ") + rt.error_string(r); return GMMVI_ERR_HIP; }
@@ -94,7 +104,8 @@ int compile_source(const char* source, Mode mode, const char* arch, std::vector<
     const char* opts[] = {arch_opt.c_str(), "-O3", "-std=c++17",
                           "-DGMMVI_CUSTOM_AUTODIFF_TANGENTS=" GMMVI_STR(GMMVI_CUSTOM_AUTODIFF_TANGENTS),   // not MODE_HAND
                           "-DGMMVI_AD_NO_ADAPTER", "-DGMMVI_WRAP_TILE_ONLY"};                              // MODE_DATA only
-    r = rt.compile(prog, mode == MODE_HAND ? 3 : mode == MODE_AUTODIFF ? 4 : 6, opts);
+    if (mode == MODE_TAPE) opts[4] = "-DGMMVI_CUSTOM_TAPE=1";
+    r = rt.compile(prog, mode == MODE_HAND ? 3 : mode == MODE_AUTODIFF ? 4 : mode == MODE_TAPE ? 5 : 6, opts);
     size_t n = 0;
     if (rt.log_size(prog, &n) == HIPRTC_SUCCESS && n > 1) {
         log.resize(n);
@@ -132,7 +143,9 @@ struct gmmvi_custom_target {
     Mode mode = MODE_HAND;
     int refs = 0;
     hipModule_t module = nullptr;
-    hipFunction_t fn[6] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad
+    hipFunction_t fn[6] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
+                                           // MODE_TAPE: lp, lp + grad
+    mutable std::vector<std::pair<int, int>> tape_lengths;   // MODE_TAPE: (D, the longest tape a gradient launch at that D has needed)
 };
 
 static std::vector<gmmvi_custom_target*>::iterator find_target(gmmvi_ctx* ctx, const gmmvi_custom_target* t) {
@@ -175,6 +188,10 @@ extern "C" int gmmvi_custom_target_check_data(const char* source, const char* ar
     return check_source("gmmvi_custom_target_check_data", source, MODE_DATA, arch, log_out, log_cap);
 }
 
+extern "C" int gmmvi_custom_target_check_tape(const char* source, const char* arch, char* log_out, size_t log_cap) {
+    return check_source("gmmvi_custom_target_check_tape", source, MODE_TAPE, arch, log_out, log_cap);
+}
+
 // The context's modules are keyed by (hash of the source, mode): the same text compiled in two modes gives two handles.
 static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_custom_target** out) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr && out != nullptr);
@@ -195,8 +212,9 @@ static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_c
                                               "gmmvi_custom_direct_grad"};
     static const char* const data_names[6] = {"gmmvi_data_rows_staged_lp", "gmmvi_data_rows_staged_grad", "gmmvi_data_rows_direct_lp",
                                               "gmmvi_data_rows_direct_grad", "gmmvi_data_merge_lp", "gmmvi_data_merge_grad"};
-    const char* const* names = mode == MODE_DATA ? data_names : wrap_names;
-    const int count = mode == MODE_DATA ? 6 : 4;
+    static const char* const tape_names[2] = {"gmmvi_tape_lp", "gmmvi_tape_grad"};
+    const char* const* names = mode == MODE_DATA ? data_names : mode == MODE_TAPE ? tape_names : wrap_names;
+    const int count = mode == MODE_DATA ? 6 : mode == MODE_TAPE ? 2 : 4;
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipModuleLoadData(&t->module, code.data());
     for (int i = 0; e == hipSuccess && i < count; ++i) e = hipModuleGetFunction(&t->fn[i], t->module, names[i]);
@@ -220,6 +238,10 @@ extern "C" int gmmvi_custom_target_compile_autodiff(gmmvi_ctx* ctx, const char* 
 
 extern "C" int gmmvi_custom_target_compile_data(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
     return compile_target(ctx, source, MODE_DATA, out);
+}
+
+extern "C" int gmmvi_custom_target_compile_tape(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
+    return compile_target(ctx, source, MODE_TAPE, out);
 }
 
 extern "C" int gmmvi_custom_target_release(gmmvi_ctx* ctx, gmmvi_custom_target* t) {
@@ -246,6 +268,10 @@ extern "C" int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* t,
     if (t->mode == MODE_DATA)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target was compiled by gmmvi_custom_target_compile_data (a row "
                                               "term and a prior, no gmmvi_user_target): gmmvi_target_custom_data launches it");
+    if (t->mode == MODE_TAPE)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target was compiled by gmmvi_custom_target_compile_tape (its "
+                                              "gradient comes from a tape, which needs scratch and a readback): "
+                                              "gmmvi_target_custom_tape launches it");
     if (route == 1 && D > GMMVI_CUSTOM_STAGED_MAX_DIM)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: route 1 (staged) needs D <= " +
                                                   std::to_string(GMMVI_CUSTOM_STAGED_MAX_DIM) + ", got D = " + std::to_string(D));
@@ -367,4 +393,109 @@ extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_targe
                                                    args, nullptr));
     }
     return GMMVI_OK;
+}
+
+// ---- targets differentiated on a tape ----------------------------------------------------------------------------------------
+// The slab plan: a wave of 64 lanes takes 64 * capacity records of GMMVI_CUSTOM_TAPE_RECORD_BYTES (16 B of record, 4 B of
+// adjoint).  As many whole waves as the budget holds form a slab; the slabs are then as even as whole waves allow, and the count
+// is what that slab size needs: the last slab is never empty.
+static size_t tape_wave_bytes(int capacity) { return (size_t)64 * (size_t)capacity * GMMVI_CUSTOM_TAPE_RECORD_BYTES; }
+
+extern "C" int gmmvi_custom_tape_plan(int N, int capacity, size_t scratch_bytes, int* slabs, int* lanes_per_slab) {
+    if (N < 1 || capacity < 1 || !slabs || !lanes_per_slab)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_tape_plan needs N >= 1, capacity >= 1 and two outputs");
+    const size_t budget = scratch_bytes ? scratch_bytes : (size_t)GMMVI_CUSTOM_TAPE_SCRATCH_BYTES;
+    const size_t fit = budget / tape_wave_bytes(capacity);
+    if (fit < 1)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "invalid argument: a tape of " + std::to_string(capacity) + " records per lane takes " +
+                                                      std::to_string(tape_wave_bytes(capacity)) + " bytes for 64 lanes, the scratch "
+                                                      "budget is " + std::to_string(budget) + " bytes");
+    const size_t waves = ((size_t)N + 63) / 64;
+    const size_t most = fit < waves ? fit : waves;
+    const size_t want = (waves + most - 1) / most;
+    const size_t per = (waves + want - 1) / want;
+    *lanes_per_slab = (int)(per * 64);
+    *slabs = (int)((waves + per - 1) / per);
+    return GMMVI_OK;
+}
+
+static int tape_length(const gmmvi_custom_target* t, int D) {
+    for (const auto& e : t->tape_lengths)
+        if (e.first == D) return e.second;
+    return 0;
+}
+
+extern "C" int gmmvi_custom_tape_length(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, int* length) {
+    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
+    GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end() && length != nullptr);
+    *length = tape_length(t, D);
+    return GMMVI_OK;
+}
+
+extern "C" int gmmvi_target_custom_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                        const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int tape_capacity,
+                                        size_t scratch_bytes) {
+    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
+    GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
+    if (t->mode != MODE_TAPE)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_tape needs a target compiled by "
+                                              "gmmvi_custom_target_compile_tape; gmmvi_target_custom and gmmvi_target_custom_data "
+                                              "launch the other kinds");
+    GMMVI_ARG_CHECK(ctx, N >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && X_dev != nullptr && lp_out_dev != nullptr);
+    GMMVI_ARG_CHECK(ctx, tape_capacity >= 0);
+    if (!grad_out_dev) {
+        const size_t blocks = ((size_t)N + 255) / 256;
+        void* args[] = {&D, &params_dev, &X_dev, &N, &lp_out_dev};
+        GMMVI_PROF(ctx, "target_custom_tape");
+        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[0], (unsigned)blocks, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr));
+        return GMMVI_OK;
+    }
+    const size_t budget = scratch_bytes ? scratch_bytes : (size_t)GMMVI_CUSTOM_TAPE_SCRATCH_BYTES;
+    size_t longest = budget / tape_wave_bytes(1);                     // the longest tape 64 lanes can have within the budget
+    if (longest > (size_t)1 << 30) longest = (size_t)1 << 30;         // node ids are ints: D + record
+    if (longest < 1)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: a scratch budget of " + std::to_string(budget) +
+                                                  " bytes holds no tape: one record of 64 lanes takes " +
+                                                  std::to_string(tape_wave_bytes(1)) + " bytes");
+    int cap = tape_capacity > 0 ? tape_capacity : tape_length(t, D);
+    if (cap < 1) cap = GMMVI_CUSTOM_TAPE_DEFAULT_CAPACITY;
+    if ((size_t)cap > longest) cap = (int)longest;                    // the launch tells what is needed: refused below if that is more
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int slabs = 0, lanes = 0;
+        if (gmmvi_custom_tape_plan(N, cap, budget, &slabs, &lanes) != GMMVI_OK)
+            return gmmvi_fail(ctx, GMMVI_ERR_ARG, g_gmmvi_global_err);
+        // scratch: [needed length, padded to 256 B | records [lanes / 64][cap][64] | adjoints, the same shape]
+        const size_t f_rec = (size_t)lanes * (size_t)cap;
+        const int rc = gmmvi_ws_reserve(ctx, 256 + f_rec * GMMVI_CUSTOM_TAPE_RECORD_BYTES);
+        if (rc != GMMVI_OK) return rc;
+        int* needed_dev = (int*)ctx->ws;
+        char* rec = (char*)ctx->ws + 256;
+        float* adj = (float*)(rec + f_rec * 16);
+        GMMVI_HIP_CHECK(ctx, hipMemsetAsync(needed_dev, 0, sizeof(int), ctx->stream));
+        for (int s = 0; s < slabs; ++s) {
+            int first = s * lanes;
+            const int rest = N - first;
+            const unsigned waves = (unsigned)(((rest < lanes ? rest : lanes) + 63) / 64);
+            void* args[] = {&D, &params_dev, &X_dev, &N, &lp_out_dev, &grad_out_dev, &first, &rec, &adj, &cap, &needed_dev};
+            GMMVI_PROF(ctx, "target_custom_tape");
+            GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[1], waves, 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
+        }
+        int needed = 0;
+        GMMVI_HIP_CHECK(ctx, hipMemcpyAsync(&needed, needed_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        GMMVI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        bool known = false;
+        for (auto& e : t->tape_lengths)
+            if (e.first == D) { known = true; if (needed > e.second) e.second = needed; }
+        if (!known) t->tape_lengths.emplace_back(D, needed);
+        if (needed <= cap) return GMMVI_OK;
+        if ((size_t)needed > longest)
+            return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target needs a tape of " + std::to_string(needed) +
+                                                      " records per lane at D = " + std::to_string(D) + ", which takes " +
+                                                      std::to_string(tape_wave_bytes(needed)) + " bytes for 64 lanes; the scratch "
+                                                      "budget is " + std::to_string(budget) + " bytes (lp_out_dev is written, "
+                                                      "grad_out_dev is not complete)");
+        cap = needed;
+    }
+    return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the tape of the target grew between two launches on the same samples: "
+                                          "gmmvi_user_density is not a pure function of x, D and params");
 }

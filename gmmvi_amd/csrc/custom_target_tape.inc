@@ -1,0 +1,257 @@
+R"GMMVI_TAPE(
+// ---- reverse-mode differentiation of a user-defined density on a tape (csrc/custom_target.hip puts this text behind the user's
+// source; contract: include/gmmvi_hip.h, "differentiated user-defined targets on a tape") ------------------------------------------
+// The text above defines   template <class T, class X> __device__ T gmmvi_user_density(X x, int D, const float* params);
+// the text of the forward mode, unchanged.  This text defines the number the library instantiates T with on a gradient call (a
+// value and the id of a node), the view X whose entries are the input nodes, and the kernels: one lane is one sample, records
+// its evaluation and walks its own records back in the same launch.
+//
+// Node ids: id < 0 a constant; 0 <= id < D the input x[id]; id >= D record id - D.  A record is {ia, ib, pa, pb}: the ids of
+// the parents and the partial derivatives of the node by them (ib = -1: one parent; a constant parent keeps its negative id
+// and takes no part in the sweep).  Record r of lane l lies at rec[r * stride + l], its adjoint at adj[r * stride + l]: on the
+// device stride = 64, a wave's record r is 1 KiB of consecutive memory and every access below is an ordinary per-lane vector
+// load or store; on the host (csrc/tape_probe.hip) stride = 1 and l = 0.
+// The partial derivatives and the tie rules are those of the forward mode (custom_target_autodiff.inc): fabs has partial 0 at
+// +-0; fmax and fmin give the first operand the partial 1 on a tie; comparisons look at the values only; pow with exponent 0
+// has partial 0 by the base; a constant exponent takes no part of ln(a).  An operation whose operands are all constants makes no
+// record.  There is no conversion from a Var to float: gmmvi_value(t) is the only way down.
+
+namespace gmmvi_tape {
+
+#define GMMVI_TAPE_FN __host__ __device__ __forceinline__
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define GMMVI_TAPE_GLOBAL __attribute__((address_space(1)))      // tape traffic is global memory: it cannot alias the LDS state below
+#else
+#define GMMVI_TAPE_GLOBAL
+#endif
+typedef int Rec4 __attribute__((ext_vector_type(4)));             // one record as it is stored: {ia, ib, bits of pa, bits of pb}
+typedef GMMVI_TAPE_GLOBAL Rec4* RecPtr;
+typedef GMMVI_TAPE_GLOBAL float* AdjPtr;
+
+struct Tape {
+    RecPtr rec;          // record 0 of lane 0
+    AdjPtr adj;          // adjoint slot 0 of lane 0
+    int stride;          // lanes per record row
+    int cap;             // records a lane may store
+    int D;               // ids below D are inputs
+};
+
+// The tape the operations below write to, and the lane's count of records made so far.  Device: the wave's tape is wave-uniform
+// state in LDS, set by the kernel before the user's function runs; the count is the lane's own LDS word, which the compiler
+// keeps in a register between the records of straight-line code (nothing else can write it).  Host: one tape per thread.
+#if defined(__HIP_DEVICE_COMPILE__)
+__device__ __forceinline__ Tape& tape() { __shared__ Tape t; return t; }
+__device__ __forceinline__ int lane() { return (int)threadIdx.x; }
+__device__ __forceinline__ int& count() { __shared__ int c[64]; return c[threadIdx.x]; }
+GMMVI_TAPE_FN float rsqrt_value(float a) { return ::rsqrtf(a); }
+#else
+inline Tape& tape() { static thread_local Tape t; return t; }
+inline int lane() { return 0; }
+inline int& count() { static thread_local int c; return c; }
+GMMVI_TAPE_FN float rsqrt_value(float a) { return 1.f / ::sqrtf(a); }
+#endif
+
+GMMVI_TAPE_FN int float_bits(float f) { union { float f; int i; } u; u.f = f; return u.i; }
+GMMVI_TAPE_FN float bits_float(int i) { union { float f; int i; } u; u.i = i; return u.f; }
+
+// Appends {ia, ib, pa, pb} and zeroes the record's adjoint; -> the id of the new node.  Beyond the capacity nothing is stored,
+// the count still advances: the values stay right and the lane knows how long its tape would have been.
+GMMVI_TAPE_FN int push(int ia, int ib, float pa, float pb) {
+    const Tape& t = tape();
+    int& c = count();
+    const int r = c;
+    if (r < t.cap) {
+        const size_t at = (size_t)r * (size_t)t.stride + (size_t)lane();
+        Rec4 v; v.x = ia; v.y = ib; v.z = float_bits(pa); v.w = float_bits(pb);
+        t.rec[at] = v;                                                  // one 16-byte store
+        t.adj[at] = 0.f;
+    }
+    c = r + 1;
+    return t.D + r;
+}
+
+struct Var {
+    float v;
+    int id;
+    Var() = default;
+    GMMVI_TAPE_FN Var(float value) : v(value), id(-1) {}                // a constant
+    GMMVI_TAPE_FN Var(float value, int node) : v(value), id(node) {}
+};
+
+// value `v` with one parent / two parents; all parents constants: a constant
+GMMVI_TAPE_FN Var node(float v, const Var& a, float pa) { return a.id < 0 ? Var(v) : Var(v, push(a.id, -1, pa, 0.f)); }
+GMMVI_TAPE_FN Var node(float v, const Var& a, float pa, const Var& b, float pb) {
+    if (a.id < 0 && b.id < 0) return Var(v);
+    return Var(v, push(a.id, b.id, a.id < 0 ? 0.f : pa, b.id < 0 ? 0.f : pb));
+}
+
+// ---- arithmetic ------------------------------------------------------------------------------------------------------------
+GMMVI_TAPE_FN Var operator-(const Var& a) { return node(-a.v, a, -1.f); }
+GMMVI_TAPE_FN Var operator+(const Var& a) { return a; }
+
+GMMVI_TAPE_FN Var operator+(const Var& a, const Var& b) { return node(a.v + b.v, a, 1.f, b, 1.f); }
+GMMVI_TAPE_FN Var operator+(const Var& a, float b) { return node(a.v + b, a, 1.f); }
+GMMVI_TAPE_FN Var operator+(float a, const Var& b) { return node(a + b.v, b, 1.f); }
+
+GMMVI_TAPE_FN Var operator-(const Var& a, const Var& b) { return node(a.v - b.v, a, 1.f, b, -1.f); }
+GMMVI_TAPE_FN Var operator-(const Var& a, float b) { return node(a.v - b, a, 1.f); }
+GMMVI_TAPE_FN Var operator-(float a, const Var& b) { return node(a - b.v, b, -1.f); }
+
+GMMVI_TAPE_FN Var operator*(const Var& a, const Var& b) { return node(a.v * b.v, a, b.v, b, a.v); }
+GMMVI_TAPE_FN Var operator*(const Var& a, float b) { return node(a.v * b, a, b); }
+GMMVI_TAPE_FN Var operator*(float a, const Var& b) { return node(a * b.v, b, a); }
+
+GMMVI_TAPE_FN Var operator/(const Var& a, const Var& b) {
+    const float v = a.v / b.v, inv = 1.f / b.v;
+    return node(v, a, inv, b, -v * inv);
+}
+GMMVI_TAPE_FN Var operator/(const Var& a, float b) { return node(a.v / b, a, 1.f / b); }
+GMMVI_TAPE_FN Var operator/(float a, const Var& b) { const float v = a / b.v; return node(v, b, -v / b.v); }
+
+GMMVI_TAPE_FN Var& operator+=(Var& a, const Var& b) { a = a + b; return a; }
+GMMVI_TAPE_FN Var& operator+=(Var& a, float b) { a = a + b; return a; }
+GMMVI_TAPE_FN Var& operator-=(Var& a, const Var& b) { a = a - b; return a; }
+GMMVI_TAPE_FN Var& operator-=(Var& a, float b) { a = a - b; return a; }
+GMMVI_TAPE_FN Var& operator*=(Var& a, const Var& b) { a = a * b; return a; }
+GMMVI_TAPE_FN Var& operator*=(Var& a, float b) { a = a * b; return a; }
+GMMVI_TAPE_FN Var& operator/=(Var& a, const Var& b) { a = a / b; return a; }
+GMMVI_TAPE_FN Var& operator/=(Var& a, float b) { a = a / b; return a; }
+
+// ---- comparisons: on the values, no record ---------------------------------------------------------------------------------------
+#define GMMVI_TAPE_COMPARE(op)                                                          \
+    GMMVI_TAPE_FN bool operator op(const Var& a, const Var& b) { return a.v op b.v; }   \
+    GMMVI_TAPE_FN bool operator op(const Var& a, float b) { return a.v op b; }          \
+    GMMVI_TAPE_FN bool operator op(float a, const Var& b) { return a op b.v; }
+GMMVI_TAPE_COMPARE(<)
+GMMVI_TAPE_COMPARE(<=)
+GMMVI_TAPE_COMPARE(>)
+GMMVI_TAPE_COMPARE(>=)
+GMMVI_TAPE_COMPARE(==)
+GMMVI_TAPE_COMPARE(!=)
+#undef GMMVI_TAPE_COMPARE
+
+// ---- functions (each also under its f-suffixed name, below) ---------------------------------------------------------------------
+GMMVI_TAPE_FN Var exp(const Var& a) { const float v = ::expf(a.v); return node(v, a, v); }
+GMMVI_TAPE_FN Var expm1(const Var& a) { return node(::expm1f(a.v), a, ::expf(a.v)); }
+GMMVI_TAPE_FN Var log(const Var& a) { return node(::logf(a.v), a, 1.f / a.v); }
+GMMVI_TAPE_FN Var log1p(const Var& a) { return node(::log1pf(a.v), a, 1.f / (1.f + a.v)); }
+GMMVI_TAPE_FN Var sqrt(const Var& a) { const float v = ::sqrtf(a.v); return node(v, a, 0.5f / v); }
+GMMVI_TAPE_FN Var rsqrt(const Var& a) { const float v = rsqrt_value(a.v); return node(v, a, -0.5f * v / a.v); }
+GMMVI_TAPE_FN Var sin(const Var& a) { return node(::sinf(a.v), a, ::cosf(a.v)); }
+GMMVI_TAPE_FN Var cos(const Var& a) { return node(::cosf(a.v), a, -::sinf(a.v)); }
+GMMVI_TAPE_FN Var tan(const Var& a) { const float v = ::tanf(a.v); return node(v, a, 1.f + v * v); }
+GMMVI_TAPE_FN Var tanh(const Var& a) {
+    const float e = ::expf(-2.f * ::fabsf(a.v));                   // sech^2 = 4 e / (1 + e)^2: no cancellation at large |a|
+    return node(::tanhf(a.v), a, 4.f * e / ((1.f + e) * (1.f + e)));
+}
+GMMVI_TAPE_FN Var atan(const Var& a) { return node(::atanf(a.v), a, 1.f / (1.f + a.v * a.v)); }
+GMMVI_TAPE_FN Var fabs(const Var& a) { return node(::fabsf(a.v), a, a.v > 0.f ? 1.f : (a.v < 0.f ? -1.f : 0.f)); }
+
+// the first operand takes the partial 1 unless the second one is strictly the winner (or the first is a NaN, which fmaxf drops)
+GMMVI_TAPE_FN Var fmax(const Var& a, const Var& b) {
+    const bool second = b.v > a.v || a.v != a.v;
+    return node(::fmaxf(a.v, b.v), a, second ? 0.f : 1.f, b, second ? 1.f : 0.f);
+}
+GMMVI_TAPE_FN Var fmin(const Var& a, const Var& b) {
+    const bool second = b.v < a.v || a.v != a.v;
+    return node(::fminf(a.v, b.v), a, second ? 0.f : 1.f, b, second ? 1.f : 0.f);
+}
+GMMVI_TAPE_FN Var fmax(const Var& a, float b) { return fmax(a, Var(b)); }
+GMMVI_TAPE_FN Var fmax(float a, const Var& b) { return fmax(Var(a), b); }
+GMMVI_TAPE_FN Var fmin(const Var& a, float b) { return fmin(a, Var(b)); }
+GMMVI_TAPE_FN Var fmin(float a, const Var& b) { return fmin(Var(a), b); }
+
+// a^b, b a float: partial b a^(b - 1), and 0 for b = 0 whatever a is
+GMMVI_TAPE_FN Var pow(const Var& a, float b) { return node(::powf(a.v, b), a, b == 0.f ? 0.f : b * ::powf(a.v, b - 1.f)); }
+// a^b: partials b a^(b - 1) and a^b ln(a); a constant exponent takes no part of ln(a) (a <= 0 stays usable there)
+GMMVI_TAPE_FN Var pow(const Var& a, const Var& b) {
+    const float v = ::powf(a.v, b.v);
+    const float da = a.id < 0 || b.v == 0.f ? 0.f : b.v * ::powf(a.v, b.v - 1.f);
+    const float db = b.id < 0 ? 0.f : v * ::logf(a.v);
+    return node(v, a, da, b, db);
+}
+GMMVI_TAPE_FN Var pow(float a, const Var& b) { return pow(Var(a), b); }
+
+#define GMMVI_TAPE_ALIAS1(name) GMMVI_TAPE_FN Var name##f(const Var& a) { return name(a); }
+GMMVI_TAPE_ALIAS1(exp) GMMVI_TAPE_ALIAS1(expm1) GMMVI_TAPE_ALIAS1(log) GMMVI_TAPE_ALIAS1(log1p) GMMVI_TAPE_ALIAS1(sqrt)
+GMMVI_TAPE_ALIAS1(rsqrt) GMMVI_TAPE_ALIAS1(sin) GMMVI_TAPE_ALIAS1(cos) GMMVI_TAPE_ALIAS1(tan) GMMVI_TAPE_ALIAS1(tanh)
+GMMVI_TAPE_ALIAS1(atan) GMMVI_TAPE_ALIAS1(fabs)
+#undef GMMVI_TAPE_ALIAS1
+#define GMMVI_TAPE_ALIAS2(name)                                                          \
+    GMMVI_TAPE_FN Var name##f(const Var& a, const Var& b) { return name(a, b); }         \
+    GMMVI_TAPE_FN Var name##f(const Var& a, float b) { return name(a, b); }              \
+    GMMVI_TAPE_FN Var name##f(float a, const Var& b) { return name(a, b); }
+GMMVI_TAPE_ALIAS2(fmax) GMMVI_TAPE_ALIAS2(fmin) GMMVI_TAPE_ALIAS2(pow)
+#undef GMMVI_TAPE_ALIAS2
+
+GMMVI_TAPE_FN float gmmvi_value(const Var& a) { return a.v; }
+
+// What a gradient call passes as x: entry i is the input node i, and reading it makes no record.
+struct Input {
+    const float* x;
+    GMMVI_TAPE_FN Var operator[](int i) const { return Var(x[i], i); }
+};
+
+}  // namespace gmmvi_tape
+
+// (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there)
+__host__ __device__ inline float gmmvi_value(float a) { return a; }
+
+#ifndef GMMVI_TAPE_NO_KERNELS
+// Value call: one float instantiation per sample, no tape.
+extern "C" __global__ __launch_bounds__(256) void gmmvi_tape_lp(int D, const float* params, const float* X, int N, float* lp) {
+    const size_t n = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= (size_t)N) return;
+    lp[n] = gmmvi_user_density<float, const float*>(X + n * (size_t)D, D, params);
+}
+
+// Gradient call: one wave per workgroup, lane = sample first + 64 blockIdx.x + lane of X[first .. N).  The lane records its
+// evaluation on the wave's tape (rec / adj + 64 cap blockIdx.x records), then walks its own records from the output back to record 0;
+// the adjoints of the inputs add up in the lane's own gradient row, which the lane zeroes first.  No other lane touches the
+// row or the lane's tape column, so no sum involves an atomic: the same inputs give the same bits.  Every lane raises *needed
+// to its record count (an integer maximum); a lane whose count exceeds cap has an incomplete tape and writes no gradient.
+extern "C" __global__ __launch_bounds__(64) void gmmvi_tape_grad(int D, const float* params, const float* X, int N, float* lp,
+                                                                  float* grad, int first, void* rec, float* adj, int cap, int* needed) {
+    using namespace gmmvi_tape;
+    const int l = (int)threadIdx.x;
+    const size_t wave_at = (size_t)blockIdx.x * 64 * (size_t)cap;
+    if (l == 0) {
+        Tape& t = tape();
+        t.rec = (RecPtr)rec + wave_at;
+        t.adj = (AdjPtr)adj + wave_at;
+        t.stride = 64; t.cap = cap; t.D = D;
+    }
+    count() = 0;
+    __syncthreads();
+    const size_t n = (size_t)first + (size_t)blockIdx.x * 64 + l;
+    if (n >= (size_t)N) return;
+    const Var out = gmmvi_user_density<Var, Input>(Input{X + n * (size_t)D}, D, params);
+    lp[n] = out.v;
+    const int made = count();
+    atomicMax(needed, made);
+    if (made > cap) return;
+    float* g = grad + n * (size_t)D;
+    for (int i = 0; i < D; ++i) g[i] = 0.f;
+    if (out.id < 0) return;                                  // a constant: the gradient is zero
+    if (out.id < D) { g[out.id] = 1.f; return; }             // an input
+    const RecPtr rp = (RecPtr)rec + wave_at + l;
+    const AdjPtr ap = (AdjPtr)adj + wave_at + l;
+    int r = out.id - D;
+    ap[(size_t)r * 64] = 1.f;
+    for (; r >= 0; --r) {
+        const Rec4 v = rp[(size_t)r * 64];
+        const float w = ap[(size_t)r * 64];
+        if (v.x >= 0) {
+            const float d = bits_float(v.z) * w;
+            if (v.x < D) g[v.x] += d; else ap[(size_t)(v.x - D) * 64] += d;
+        }
+        if (v.y >= 0) {
+            const float d = bits_float(v.w) * w;
+            if (v.y < D) g[v.y] += d; else ap[(size_t)(v.y - D) * 64] += d;
+        }
+    }
+}
+#endif
+#undef GMMVI_TAPE_FN
+)GMMVI_TAPE"

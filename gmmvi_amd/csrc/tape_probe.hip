@@ -1,0 +1,73 @@
+// gmmvi_tape_probe (include/gmmvi_hip.h): one operation of the tape's number type (custom_target_tape.inc, its raw-string
+// delimiters taken off by the Makefile, without the kernels, which need a user's function), run on a tape in host memory.  The
+// operations and their order are those of autodiff_probe.hip.  Host code only.
+#include "common.h"
+
+#define GMMVI_TAPE_NO_KERNELS
+#include "build/custom_target_tape_text.inc"
+
+namespace {
+using gmmvi_tape::Var;
+
+Var flag(bool c) { return Var(c ? 1.f : 0.f); }
+
+#define PROBE_ARITH(op)                                         \
+    case __COUNTER__ - kBase: r = A op B; break;                \
+    case __COUNTER__ - kBase: r = A op b; break;                \
+    case __COUNTER__ - kBase: r = a op B; break;                \
+    case __COUNTER__ - kBase: r = A; r op## = B; break;         \
+    case __COUNTER__ - kBase: r = A; r op## = b; break;
+#define PROBE_COMPARE(op)                                       \
+    case __COUNTER__ - kBase: r = flag(A op B); break;          \
+    case __COUNTER__ - kBase: r = flag(A op b); break;          \
+    case __COUNTER__ - kBase: r = flag(a op B); break;
+#define PROBE_UNARY(fn)                                         \
+    case __COUNTER__ - kBase: r = fn(A); break;                 \
+    case __COUNTER__ - kBase: r = fn##f(A); break;
+#define PROBE_BINARY(fn)                                        \
+    case __COUNTER__ - kBase: r = fn(A, B); break;              \
+    case __COUNTER__ - kBase: r = fn(A, b); break;              \
+    case __COUNTER__ - kBase: r = fn(a, B); break;              \
+    case __COUNTER__ - kBase: r = fn##f(A, B); break;           \
+    case __COUNTER__ - kBase: r = fn##f(A, b); break;           \
+    case __COUNTER__ - kBase: r = fn##f(a, B); break;
+
+constexpr int kBase = __COUNTER__ + 1;
+}  // namespace
+
+extern "C" int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb,
+                                int* records) {
+    if (!value || !pa || !pb || !records)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe: value, pa, pb and records must not be NULL");
+    constexpr int kCap = 4;
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, 2};   // stride 1, D = 2
+    gmmvi_tape::count() = 0;
+    const Var A = a_is_const ? Var(a) : Var(a, 0), B = b_is_const ? Var(b) : Var(b, 1);
+    Var r;
+    switch (op) {
+        PROBE_ARITH(+) PROBE_ARITH(-) PROBE_ARITH(*) PROBE_ARITH(/)
+        case __COUNTER__ - kBase: r = -A; break;
+        PROBE_COMPARE(<) PROBE_COMPARE(<=) PROBE_COMPARE(>) PROBE_COMPARE(>=) PROBE_COMPARE(==) PROBE_COMPARE(!=)
+        PROBE_UNARY(exp) PROBE_UNARY(expm1) PROBE_UNARY(log) PROBE_UNARY(log1p) PROBE_UNARY(sqrt) PROBE_UNARY(rsqrt)
+        PROBE_UNARY(sin) PROBE_UNARY(cos) PROBE_UNARY(tan) PROBE_UNARY(tanh) PROBE_UNARY(atan) PROBE_UNARY(fabs)
+        PROBE_BINARY(fmax) PROBE_BINARY(fmin) PROBE_BINARY(pow)
+        case __COUNTER__ - kBase: r = Var(gmmvi_value(A)); break;
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe: unknown operation " + std::to_string(op));
+    }
+    *value = r.v;
+    *records = gmmvi_tape::count();
+    *pa = *pb = 0.f;
+    // the partials of the operation's one record, by the id of the parent they belong to (a is node 0, b is node 1)
+    if (*records == 1) {
+        const int ids[2] = {rec[0].x, rec[0].y};
+        const float partials[2] = {gmmvi_tape::bits_float(rec[0].z), gmmvi_tape::bits_float(rec[0].w)};
+        for (int j = 0; j < 2; ++j) {
+            if (ids[j] == 0) *pa += partials[j];
+            if (ids[j] == 1) *pb += partials[j];
+        }
+    }
+    return GMMVI_OK;
+}

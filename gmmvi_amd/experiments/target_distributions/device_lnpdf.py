@@ -16,6 +16,10 @@ iteration take it as target kind 5.
 and the library differentiates it in forward mode (csrc/custom_target_autodiff.inc): upstream's "write log_density, the framework
 differentiates it" (SampleSelector.get_target_grads) on the device.
 
+``DeviceTapeLNPDF`` takes the same density text and differentiates it in reverse mode on a tape (csrc/custom_target_tape.inc):
+the cost of the gradient does not grow with the dimension, so it runs up to the largest diagonal-covariance dimension, on the
+modular path.
+
 ``DeviceDataLNPDF`` takes one data row's log-likelihood and the prior,
 
     template <class T, class X> __device__ T gmmvi_user_row  (X x, int D, const float* row, int C, const float* params);
@@ -113,6 +117,44 @@ class DeviceAutodiffLNPDF(_DeviceLNPDFWithGradient):
 
     def _compile(self):
         return hip_ops.custom_target_compile(self.ctx, self.source, autodiff=True)
+
+
+class DeviceTapeLNPDF(DeviceLNPDF):
+    """``DeviceTapeLNPDF(source, num_dimensions, params=None, tape_capacity=None, scratch_bytes=None)``: ``source`` defines
+    ``gmmvi_user_density``, the text a ``DeviceAutodiffLNPDF`` takes, and the gradient comes from reverse mode: every sample
+    records its evaluation on a tape in device scratch and walks it back (csrc/custom_target_tape.inc), one recorded evaluation
+    and one sweep whatever the dimension, up to ``_lib.MAX_DIM_DIAG``.
+
+    tape_capacity: records per sample of the first gradient call (None: the library's default, then what the target has needed);
+    scratch_bytes: the budget of the tape scratch (None: ``_lib.CUSTOM_TAPE_SCRATCH_BYTES``); more samples than fit are
+    processed in slabs.  A gradient call reads the needed tape length back from the device and so waits for the stream: there is
+    no ``_fast_path_target``, the iteration runs module by module."""
+
+    # the gradient costs a tape the value call does not write: an estimator that reads no target gradients gets values only
+    gradient_on_demand = True
+
+    def __new__(cls, *args, **kwargs):
+        return object.__new__(cls)
+
+    def __init__(self, source, num_dimensions, params=None, tape_capacity=None, scratch_bytes=None):
+        for name, value in (("tape_capacity", tape_capacity), ("scratch_bytes", scratch_bytes)):
+            if value is not None and (int(value) != value or int(value) < 1):
+                raise ValueError(f"{name} must be a positive integer or None, got {value!r}")
+        self.tape_capacity = 0 if tape_capacity is None else int(tape_capacity)
+        self.scratch_bytes = 0 if scratch_bytes is None else int(scratch_bytes)
+        super().__init__(source, num_dimensions, params, has_gradient=True)
+
+    def _compile(self):
+        return hip_ops.custom_target_compile(self.ctx, self.source, mode="tape")
+
+    def log_density(self, x):
+        return hip_ops.target_custom_tape(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=False)[0]
+
+    def log_density_and_grad(self, x):
+        # the asked-for capacity sizes the first launch; afterwards the handle knows what the target needs
+        first = self.tape_capacity and hip_ops.custom_tape_length(self.ctx, self._handle, self._num_dimensions) == 0
+        return hip_ops.target_custom_tape(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=True,
+                                          tape_capacity=self.tape_capacity if first else 0, scratch_bytes=self.scratch_bytes)
 
 
 class DeviceDataLNPDF(MinibatchLNPDF):

@@ -119,6 +119,25 @@ def custom_target_check_data(source, arch="gfx950"):
     return int(rc), log.value.decode(errors="replace")
 
 
+def custom_target_check_tape(source, arch="gfx950"):
+    """custom_target_check for a source that defines ``gmmvi_user_density``, compiled for the tape mode (reverse-mode
+    differentiation, csrc/custom_target_tape.inc).  -> (status, compiler log)."""
+    import ctypes as C
+    log = C.create_string_buffer(1 << 16)
+    rc = _lib.load().gmmvi_custom_target_check_tape(str(source).encode(), str(arch).encode(), log, len(log))
+    return int(rc), log.value.decode(errors="replace")
+
+
+def custom_tape_plan(n, capacity, scratch_bytes=0):
+    """The slab plan of a tape-mode gradient call on n samples at ``capacity`` records per lane within ``scratch_bytes`` (0: the
+    default budget) (gmmvi_custom_tape_plan; needs no device) -> (slabs, lanes_per_slab)."""
+    import ctypes as C
+    slabs, lanes = C.c_int(), C.c_int()
+    lib = _lib.load()
+    _lib.check(None, lib.gmmvi_custom_tape_plan(int(n), int(capacity), int(scratch_bytes), C.byref(slabs), C.byref(lanes)))
+    return slabs.value, lanes.value
+
+
 def custom_data_plan(n, rows, chunks_requested=0):
     """The launch plan of ``target_custom_data`` for n samples and a row list of ``rows`` (gmmvi_custom_data_plan; needs no
     device) -> (chunks, rows_per_chunk)."""
@@ -148,14 +167,14 @@ class CustomTarget:
             pass
 
 
-CUSTOM_TARGET_MODES = ("hand", "autodiff", "data")
+CUSTOM_TARGET_MODES = ("hand", "autodiff", "data", "tape")
 
 
 def custom_target_compile(ctx, source, autodiff=False, mode=None):
     """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  mode: "hand" (the
     source defines ``gmmvi_user_target``), "autodiff" (``gmmvi_user_density``, the library differentiates it) or "data"
-    (``gmmvi_user_row`` and ``gmmvi_user_prior``, launched by ``target_custom_data``); None: ``autodiff`` chooses between the
-    first two.  A source that does not compile raises GmmviError with the compiler log."""
+    (``gmmvi_user_row`` and ``gmmvi_user_prior``, launched by ``target_custom_data``) or "tape" (``gmmvi_user_density``,
+    differentiated in reverse mode, launched by ``target_custom_tape``); None: ``autodiff`` chooses between the first two.  A source that does not compile raises GmmviError with the compiler log."""
     import ctypes as C
     if mode is None:
         mode = "autodiff" if autodiff else "hand"
@@ -163,7 +182,7 @@ def custom_target_compile(ctx, source, autodiff=False, mode=None):
         raise ValueError(f"mode: expected one of {CUSTOM_TARGET_MODES}, got {mode!r}")
     h = C.c_void_p()
     compile_fn = {"hand": ctx.lib.gmmvi_custom_target_compile, "autodiff": ctx.lib.gmmvi_custom_target_compile_autodiff,
-                  "data": ctx.lib.gmmvi_custom_target_compile_data}[mode]
+                  "data": ctx.lib.gmmvi_custom_target_compile_data, "tape": ctx.lib.gmmvi_custom_target_compile_tape}[mode]
     ctx.check(compile_fn(ctx.handle, str(source).encode(), C.byref(h)))
     return CustomTarget(ctx, h)
 
@@ -212,6 +231,36 @@ def target_custom_data(ctx, handle, params, data, x, want_grad=True, batch_size=
             0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
             int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks)))
     return lp, grad
+
+
+def target_custom_tape(ctx, handle, params, x, want_grad=True, tape_capacity=0, scratch_bytes=0):
+    """Tape-mode user target ``handle`` on x [n, D] (csrc/custom_target_tape.inc): the gradient from one recorded evaluation
+    and one backward sweep per sample.  tape_capacity: records per lane, 0 what the handle has needed at this D so far;
+    scratch_bytes: the budget of the tape scratch, 0 the default.  A gradient call synchronises the stream.
+    -> (lp [n], grad [n, D] or None)."""
+    if not isinstance(handle, CustomTarget):
+        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
+    n, d = x.shape
+    _req(x, (n, d), name="x")
+    if params is not None:
+        if len(params.shape) != 1:
+            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
+        _req(params, params.shape, name="params")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_custom_tape(ctx.handle, handle.handle, d, None if params is None else params.ptr, x.ptr, n,
+                                                   lp.ptr, None if grad is None else grad.ptr, int(tape_capacity),
+                                                   int(scratch_bytes)))
+    return lp, grad
+
+
+def custom_tape_length(ctx, handle, d):
+    """The longest tape (records per lane) a gradient launch of ``handle`` has needed at dimension d; 0: none yet."""
+    import ctypes as C
+    length = C.c_int()
+    ctx.check(ctx.lib.gmmvi_custom_tape_length(ctx.handle, handle.handle, int(d), C.byref(length)))
+    return length.value
 
 
 def target_logreg(ctx, A, prior_mean, prior_std, x, want_grad=True):

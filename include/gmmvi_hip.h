@@ -425,6 +425,72 @@ int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* target, 
                              const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed, uint32_t call,
                              const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int chunks_requested);
 
+/* ---- differentiated user-defined targets on a tape: reverse mode ------------------------------------------------------------------
+ * The forward mode above costs ceil(D / W) passes and stops at GMMVI_CUSTOM_AUTODIFF_MAX_DIM.  This mode takes the same source,
+ *
+ *     template <class T, class X> __device__ T gmmvi_user_density(X x, int D, const float* params);
+ *
+ * under the same rules, unchanged (a text that runs in the forward mode compiles and runs here; the compiler is additionally given
+ * -DGMMVI_CUSTOM_TAPE=1, so a text can tell the modes apart), and gives the whole gradient from ONE recorded evaluation and one
+ * backward sweep, at any D up to GMMVI_MAX_DIM_DIAG.  The library puts csrc/custom_target_tape.inc behind the source:
+ *   - for a value call T = float, X = const float*, exactly as in the forward mode;
+ *   - for a gradient call T = gmmvi_tape::Var, a value and a node id (id < 0: a constant; 0 <= id < D: the input x[id];
+ *     id >= D: record id - D), and X is a view whose entry i is the input node i; reading it makes no record.
+ * On a T the text defines the operations of the forward mode's list above, no more and no fewer, with the same partial
+ * derivatives and tie rules (fabs at +-0, fmax / fmin ties, pow with exponent 0, the tanh form); a constant operand gets no
+ * partial (the tape's form of "a direction in which the exponent does not move"), and an operation on constants alone makes no
+ * record.  A T does not convert to float; gmmvi_value is the only way down.
+ * One record is {int ia, ib; float pa, pb}: the parents' ids (ib = -1: one parent) and the partials, 16 bytes written by one
+ * 16-byte store.  A wave's tape is laid out [record][64 lanes]: record r of a wave is 1 KiB of consecutive memory; the adjoints
+ * have the same layout, 4 bytes per slot, and a record's adjoint is zeroed when the record is written.  Per lane and record that
+ * is GMMVI_CUSTOM_TAPE_RECORD_BYTES of scratch.  The lane's record count is its own; all tape traffic is ordinary per-lane vector
+ * loads and stores.
+ * Kernels: one lane is one sample, one wave per workgroup.  The lane records the user's function (every store guarded by the
+ * capacity; beyond it the value stays right and the count keeps counting), then, in the same launch, seeds the output's adjoint
+ * with 1 and walks its own records from the output back to the first.  Adjoints of inputs add up in the lane's own row of
+ * grad_out_dev, which the lane zeroes first.  No atomic takes part in a floating-point sum: the same inputs give the same bits.
+ * An output that is an input or a constant is handled; lanes past N write nothing.  Every lane raises the call's needed length
+ * to its own count with an integer atomic maximum; a lane whose count exceeds the capacity writes no gradient.
+ * Capacity: tape_capacity == 0 means what this handle has needed at this D so far (first use: GMMVI_CUSTOM_TAPE_DEFAULT_CAPACITY).
+ * After a gradient launch the call reads the needed length back (4 bytes); if it exceeds the capacity, the scratch grows and the
+ * launch is repeated once: values are deterministic, so the second run is the result.  The handle remembers the longest length
+ * per D, so a steady-state call launches once.  THE READBACK IS A STREAM SYNCHRONISATION: this mode is a target of the modular
+ * path only.  gmmvi_target_custom, and so target kind 5 of the single-call and the sharded iteration, refuse a tape handle.
+ * Scratch: scratch_bytes == 0 means GMMVI_CUSTOM_TAPE_SCRATCH_BYTES, a setting, not a measurement.  If the lanes of N samples
+ * (rounded up to whole waves) times capacity times GMMVI_CUSTOM_TAPE_RECORD_BYTES exceed the budget, the samples are processed
+ * in slabs of a multiple of 64 lanes, launched one after another on the stream (gmmvi_custom_tape_plan).  A capacity that does
+ * not fit the budget for 64 lanes is cut to what fits; if the launch then reports a longer tape, the call fails with
+ * GMMVI_ERR_ARG, and the message states the needed length and its bytes (lp_out_dev is then written, grad_out_dev incomplete).
+ * The scratch is the context's, reused across calls. */
+#define GMMVI_CUSTOM_TAPE_RECORD_BYTES 20            /* 16 B of record + 4 B of adjoint */
+#define GMMVI_CUSTOM_TAPE_DEFAULT_CAPACITY 1024      /* records per lane of a handle's first gradient launch at a D */
+#define GMMVI_CUSTOM_TAPE_SCRATCH_BYTES 2147483648ull /* default budget of the tape scratch: 2 GiB */
+/* gmmvi_custom_target_check / _compile for this mode (a source without gmmvi_user_density: GMMVI_ERR_ARG, the log names it).
+ * The handle is an ordinary gmmvi_custom_target, released by gmmvi_custom_target_release; the mode is part of the context's
+ * key: the same text compiled for the forward mode and for the tape gives two handles. */
+int gmmvi_custom_target_check_tape(const char* source, const char* arch, char* log_out, size_t log_cap);
+int gmmvi_custom_target_compile_tape(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out);
+/* The slab plan, a host function (no device, no context): as many whole waves as scratch_bytes (0: the default) holds at
+ * `capacity` records per lane form a slab, the slabs are as even as whole waves allow, *lanes_per_slab is a multiple of 64,
+ * *slabs * *lanes_per_slab >= N and the last slab is never empty.  N < 1, capacity < 1, a NULL output, or a budget below the
+ * need of 64 lanes: GMMVI_ERR_ARG. */
+int gmmvi_custom_tape_plan(int N, int capacity, size_t scratch_bytes, int* slabs, int* lanes_per_slab);
+/* *length = the longest tape (records per lane) a gradient launch of this handle has needed at D; 0: none yet. */
+int gmmvi_custom_tape_length(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, int* length);
+/* lp[n] (and grad[n] when grad_out_dev != NULL) of the density.  X_dev[N,D], lp_out_dev[N], grad_out_dev[N,D] or NULL (one
+ * launch of the float instantiation, no tape, no synchronisation).  GMMVI_ERR_ARG before any launch: N < 1; D outside
+ * 1 .. GMMVI_MAX_DIM_DIAG; tape_capacity < 0; a NULL X_dev or lp_out_dev; a handle of another mode (the message names the entry
+ * points) or context.  Profiling tag: target_custom_tape. */
+int gmmvi_target_custom_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                             const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int tape_capacity,
+                             size_t scratch_bytes);
+/* One operation of the tape's number type on a host tape (no device, no context): op indexes the operations in the order of
+ * gmmvi_autodiff_probe; a / b: the operands, each the input node 0 / 1 or, with its flag set, a constant (a float operand of the
+ * operation is a float whatever its flag says).  *value: the result; *pa, *pb: the partials the operation recorded for a and b
+ * (0 where it recorded none: a constant or float operand, a comparison, gmmvi_value); *records: the records it made.  An
+ * unknown op or a NULL output: GMMVI_ERR_ARG. */
+int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb, int* records);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
