@@ -201,6 +201,11 @@ _PROTOS = {
     "gmmvi_custom_tape_length": (_i, [_p, _p, _i, C.POINTER(_i)]),
     "gmmvi_target_custom_tape": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _sz]),
     "gmmvi_tape_probe": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "gmmvi_custom_target_check_data_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
+    "gmmvi_custom_target_compile_data_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
+    "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "gmmvi_target_custom_data_tape": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i, _i, _sz]),
+    "gmmvi_data_tape_probe": (_i, [_i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _i, _i, _i, _p, _p, C.POINTER(_i)]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),

@@ -10,6 +10,9 @@
 // gmmvi_target_custom_data launches.
 // Targets differentiated on a tape (gmmvi_custom_target_compile_tape): the source of the differentiated mode, unchanged; behind it
 // goes custom_target_tape.inc alone, the tape's number type and its two kernels, which gmmvi_target_custom_tape launches.
+// Targets summed over a data set and differentiated on a tape (gmmvi_custom_target_compile_data_tape): the source of the data
+// mode, unchanged; behind it go the whole text of the data mode (its value kernels are this mode's value call), the tape's number
+// type without its kernels and custom_target_data_tape.inc, whose two kernels gmmvi_target_custom_data_tape launches.
 #include "common.h"
 #include "feistel.h"
 #include <hip/hiprtc.h>
@@ -29,14 +32,18 @@ static const char* const kDataText =
 static const char* const kTapeText =
 #include "custom_target_tape.inc"
     ;
+static const char* const kDataTapeText =
+#include "custom_target_data_tape.inc"
+    ;
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
 // the float instantiation of the user's template finds gmmvi_value only if it is declared before the template.
 static const char* const kAutodiffPrelude = "__host__ __device__ inline float gmmvi_value(float); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
 
-// what the source defines: gmmvi_user_target; gmmvi_user_density; gmmvi_user_row and gmmvi_user_prior; gmmvi_user_density again
-enum Mode { MODE_HAND = 0, MODE_AUTODIFF = 1, MODE_DATA = 2, MODE_TAPE = 3 };
+// what the source defines: gmmvi_user_target; gmmvi_user_density; gmmvi_user_row and gmmvi_user_prior; gmmvi_user_density again;
+// gmmvi_user_row and gmmvi_user_prior again
+enum Mode { MODE_HAND = 0, MODE_AUTODIFF = 1, MODE_DATA = 2, MODE_TAPE = 3, MODE_DATA_TAPE = 4 };
 
 namespace {
 struct Hiprtc {
@@ -93,19 +100,22 @@ int compile_source(const char* source, Mode mode, const char* arch, std::vector<
     } else {
         if (mode != MODE_HAND) text += kAutodiffText;
         text += std::string("\n") + kWrapText;
-        if (mode == MODE_DATA) text += std::string("\n") + kDataText;
+        if (mode == MODE_DATA || mode == MODE_DATA_TAPE) text += std::string("\n") + kDataText;
+        if (mode == MODE_DATA_TAPE) text += std::string("\n") + kTapeText + "\n" + kDataTapeText;
     }
-    static const char* const entries[4][2] = {{"gmmvi_user_target", nullptr}, {"gmmvi_user_density", nullptr},
-                                              {"gmmvi_user_row", "gmmvi_user_prior"}, {"gmmvi_user_density", nullptr}};
+    static const char* const entries[5][2] = {{"gmmvi_user_target", nullptr}, {"gmmvi_user_density", nullptr},
+                                              {"gmmvi_user_row", "gmmvi_user_prior"}, {"gmmvi_user_density", nullptr},
+                                              {"gmmvi_user_row", "gmmvi_user_prior"}};
     hiprtcProgram prog = nullptr;
     hiprtcResult r = rt.create(&prog, text.c_str(), "gmmvi_user_target.hip", 0, nullptr, nullptr);
     if (r != HIPRTC_SUCCESS) { log = std::string("hiprtcCreateProgram: ") + rt.error_string(r); return GMMVI_ERR_HIP; }
     const std::string arch_opt = std::string("--offload-arch=") + arch;
     const char* opts[] = {arch_opt.c_str(), "-O3", "-std=c++17",
                           "-DGMMVI_CUSTOM_AUTODIFF_TANGENTS=" GMMVI_STR(GMMVI_CUSTOM_AUTODIFF_TANGENTS),   // not MODE_HAND
-                          "-DGMMVI_AD_NO_ADAPTER", "-DGMMVI_WRAP_TILE_ONLY"};                              // MODE_DATA only
+                          "-DGMMVI_AD_NO_ADAPTER", "-DGMMVI_WRAP_TILE_ONLY",                               // the data modes only
+                          "-DGMMVI_TAPE_NO_KERNELS", "-DGMMVI_TAPE_NO_FLOAT_VALUE", "-DGMMVI_CUSTOM_TAPE=1"};   // MODE_DATA_TAPE only
     if (mode == MODE_TAPE) opts[4] = "-DGMMVI_CUSTOM_TAPE=1";
-    r = rt.compile(prog, mode == MODE_HAND ? 3 : mode == MODE_AUTODIFF ? 4 : mode == MODE_TAPE ? 5 : 6, opts);
+    r = rt.compile(prog, mode == MODE_HAND ? 3 : mode == MODE_AUTODIFF ? 4 : mode == MODE_TAPE ? 5 : mode == MODE_DATA ? 6 : 9, opts);
     size_t n = 0;
     if (rt.log_size(prog, &n) == HIPRTC_SUCCESS && n > 1) {
         log.resize(n);
@@ -143,9 +153,9 @@ struct gmmvi_custom_target {
     Mode mode = MODE_HAND;
     int refs = 0;
     hipModule_t module = nullptr;
-    hipFunction_t fn[6] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
-                                           // MODE_TAPE: lp, lp + grad
-    mutable std::vector<std::pair<int, int>> tape_lengths;   // MODE_TAPE: (D, the longest tape a gradient launch at that D has needed)
+    hipFunction_t fn[8] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
+                                           // MODE_TAPE: lp, lp + grad; MODE_DATA_TAPE: the six of MODE_DATA, tape rows, tape finish
+    mutable std::vector<std::pair<int, int>> tape_lengths;   // the tape modes: (D, the longest tape a gradient launch at that D has needed)
 };
 
 static std::vector<gmmvi_custom_target*>::iterator find_target(gmmvi_ctx* ctx, const gmmvi_custom_target* t) {
@@ -192,6 +202,10 @@ extern "C" int gmmvi_custom_target_check_tape(const char* source, const char* ar
     return check_source("gmmvi_custom_target_check_tape", source, MODE_TAPE, arch, log_out, log_cap);
 }
 
+extern "C" int gmmvi_custom_target_check_data_tape(const char* source, const char* arch, char* log_out, size_t log_cap) {
+    return check_source("gmmvi_custom_target_check_data_tape", source, MODE_DATA_TAPE, arch, log_out, log_cap);
+}
+
 // The context's modules are keyed by (hash of the source, mode): the same text compiled in two modes gives two handles.
 static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_custom_target** out) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr && out != nullptr);
@@ -213,8 +227,12 @@ static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_c
     static const char* const data_names[6] = {"gmmvi_data_rows_staged_lp", "gmmvi_data_rows_staged_grad", "gmmvi_data_rows_direct_lp",
                                               "gmmvi_data_rows_direct_grad", "gmmvi_data_merge_lp", "gmmvi_data_merge_grad"};
     static const char* const tape_names[2] = {"gmmvi_tape_lp", "gmmvi_tape_grad"};
-    const char* const* names = mode == MODE_DATA ? data_names : mode == MODE_TAPE ? tape_names : wrap_names;
-    const int count = mode == MODE_DATA ? 6 : mode == MODE_TAPE ? 2 : 4;
+    static const char* const data_tape_names[8] = {"gmmvi_data_rows_staged_lp", "gmmvi_data_rows_staged_grad",
+                                                   "gmmvi_data_rows_direct_lp", "gmmvi_data_rows_direct_grad", "gmmvi_data_merge_lp",
+                                                   "gmmvi_data_merge_grad", "gmmvi_data_tape_rows", "gmmvi_data_tape_finish"};
+    const char* const* names = mode == MODE_DATA ? data_names : mode == MODE_TAPE ? tape_names :
+                               mode == MODE_DATA_TAPE ? data_tape_names : wrap_names;
+    const int count = mode == MODE_DATA ? 6 : mode == MODE_TAPE ? 2 : mode == MODE_DATA_TAPE ? 8 : 4;
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipModuleLoadData(&t->module, code.data());
     for (int i = 0; e == hipSuccess && i < count; ++i) e = hipModuleGetFunction(&t->fn[i], t->module, names[i]);
@@ -244,6 +262,17 @@ extern "C" int gmmvi_custom_target_compile_tape(gmmvi_ctx* ctx, const char* sour
     return compile_target(ctx, source, MODE_TAPE, out);
 }
 
+extern "C" int gmmvi_custom_target_compile_data_tape(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out) {
+    return compile_target(ctx, source, MODE_DATA_TAPE, out);
+}
+
+// what gmmvi_target_custom, gmmvi_target_custom_data and gmmvi_target_custom_tape answer to a handle of MODE_DATA_TAPE
+static int refuse_data_tape(gmmvi_ctx* ctx) {
+    return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target was compiled by gmmvi_custom_target_compile_data_tape (a row "
+                                          "term and a prior, differentiated on a tape that needs scratch and a readback): "
+                                          "gmmvi_target_custom_data_tape launches it");
+}
+
 extern "C" int gmmvi_custom_target_release(gmmvi_ctx* ctx, gmmvi_custom_target* t) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr);
     if (!t) return GMMVI_OK;
@@ -265,6 +294,7 @@ extern "C" int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* t,
     GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
     GMMVI_ARG_CHECK(ctx, N >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && X_dev != nullptr && lp_out_dev != nullptr);
     GMMVI_ARG_CHECK(ctx, route >= 0 && route <= 2);
+    if (t->mode == MODE_DATA_TAPE) return refuse_data_tape(ctx);
     if (t->mode == MODE_DATA)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target was compiled by gmmvi_custom_target_compile_data (a row "
                                               "term and a prior, no gmmvi_user_target): gmmvi_target_custom_data launches it");
@@ -334,15 +364,9 @@ struct RowList {                 // gmmvi_data::RowList of custom_target_data.in
 static_assert(sizeof(RowList) == 36, "RowList is a kernel argument: its layout is the device text's");
 }  // namespace
 
-extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
-                                        const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
-                                        uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
-                                        int chunks_requested) {
-    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
-    GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
-    if (t->mode != MODE_DATA)
-        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_data needs a target compiled by "
-                                              "gmmvi_custom_target_compile_data; gmmvi_target_custom launches the other two kinds");
+// the refusals the two data modes share, in the order and with the messages of gmmvi_target_custom_data
+static int check_data_arguments(gmmvi_ctx* ctx, int D, const float* data_dev, int64_t T, int C, int minibatch, int64_t B,
+                                const float* X_dev, int N, const float* lp_out_dev, int chunks_requested) {
     GMMVI_ARG_CHECK(ctx, N >= 1 && D >= 1 && D <= GMMVI_MAX_DIM_DIAG && X_dev != nullptr && lp_out_dev != nullptr);
     GMMVI_ARG_CHECK(ctx, data_dev != nullptr && (minibatch == 0 || minibatch == 1) && chunks_requested >= 0);
     if (T < 1 || T > 2147483647ll)
@@ -352,11 +376,14 @@ extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_targe
     if (B < 1 || B > T)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the batch size needs 1 <= B <= T = " + std::to_string(T) +
                                                   ", got B = " + std::to_string(B) + " (pass B = T with the full-data mode)");
+    return GMMVI_OK;
+}
+
+// the launches of the data mode's kernels (fn[0 .. 5] of a handle of either data mode), dual-number gradient or value alone
+static int launch_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev, const float* data_dev, int64_t T,
+                       int C, int minibatch, int64_t B, uint64_t seed, uint32_t call, const float* X_dev, int N, float* lp_out_dev,
+                       float* grad_out_dev, int chunks_requested) {
     const bool want_grad = grad_out_dev != nullptr;
-    if (want_grad && D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM)
-        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the gradient of a differentiated target needs D <= " +
-                                                  std::to_string(GMMVI_CUSTOM_AUTODIFF_MAX_DIM) + ", got D = " + std::to_string(D) +
-                                                  " (a value call runs above)");
     const int64_t length = minibatch ? B : T;
     int chunks = 0, rows_per_chunk = 0;
     if (gmmvi_custom_data_plan(N, length, chunks_requested, &chunks, &rows_per_chunk) != GMMVI_OK)
@@ -393,6 +420,26 @@ extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_targe
                                                    args, nullptr));
     }
     return GMMVI_OK;
+}
+
+extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                        const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
+                                        uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                        int chunks_requested) {
+    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
+    GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
+    if (t->mode == MODE_DATA_TAPE) return refuse_data_tape(ctx);
+    if (t->mode != MODE_DATA)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_data needs a target compiled by "
+                                              "gmmvi_custom_target_compile_data; gmmvi_target_custom launches the other two kinds");
+    const int rc = check_data_arguments(ctx, D, data_dev, T, C, minibatch, B, X_dev, N, lp_out_dev, chunks_requested);
+    if (rc != GMMVI_OK) return rc;
+    if (grad_out_dev != nullptr && D > GMMVI_CUSTOM_AUTODIFF_MAX_DIM)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the gradient of a differentiated target needs D <= " +
+                                                  std::to_string(GMMVI_CUSTOM_AUTODIFF_MAX_DIM) + ", got D = " + std::to_string(D) +
+                                                  " (a value call runs above)");
+    return launch_data(ctx, t, D, params_dev, data_dev, T, C, minibatch, B, seed, call, X_dev, N, lp_out_dev, grad_out_dev,
+                       chunks_requested);
 }
 
 // ---- targets differentiated on a tape ----------------------------------------------------------------------------------------
@@ -437,6 +484,7 @@ extern "C" int gmmvi_target_custom_tape(gmmvi_ctx* ctx, const gmmvi_custom_targe
                                         size_t scratch_bytes) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr);
     GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
+    if (t->mode == MODE_DATA_TAPE) return refuse_data_tape(ctx);
     if (t->mode != MODE_TAPE)
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_tape needs a target compiled by "
                                               "gmmvi_custom_target_compile_tape; gmmvi_target_custom and gmmvi_target_custom_data "
@@ -498,4 +546,140 @@ extern "C" int gmmvi_target_custom_tape(gmmvi_ctx* ctx, const gmmvi_custom_targe
     }
     return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the tape of the target grew between two launches on the same samples: "
                                           "gmmvi_user_density is not a pure function of x, D and params");
+}
+
+// ---- targets summed over a data set, differentiated on a tape --------------------------------------------------------------------
+// The plan.  A wave (one tile of 64 samples, one chunk of the row list) takes 64 * (capacity * GMMVI_CUSTOM_TAPE_RECORD_BYTES +
+// 4 D) bytes: its tape and its [D][64] gradient accumulator.  Chunks first: the request, or enough chunks that tiles * chunks
+// waves reach GMMVI_DATA_TAPE_PLAN_WAVES (four waves on each compute unit of an MI355X) but no more than rows /
+// GMMVI_DATA_TAPE_MIN_CHUNK_ROWS; either way at most one per row and at most as many as the budget holds waves, then as even as
+// whole rows allow.  Then slabs: as many tiles as the budget holds with that many chunks each, as even as whole tiles allow.
+// Neither constant is measured: they restate the rule of gmmvi_custom_data_plan for one-wave workgroups.
+constexpr int64_t GMMVI_DATA_TAPE_PLAN_WAVES = 4 * GMMVI_DATA_PLAN_CUS;
+constexpr int64_t GMMVI_DATA_TAPE_MIN_CHUNK_ROWS = 8;
+
+static size_t data_tape_wave_bytes(int D, int capacity) {
+    return (size_t)64 * ((size_t)capacity * GMMVI_CUSTOM_TAPE_RECORD_BYTES + 4 * (size_t)D);
+}
+
+extern "C" int gmmvi_custom_data_tape_plan(int N, int64_t rows, int D, int capacity, int chunks_requested, size_t scratch_bytes,
+                                           int* chunks, int* rows_per_chunk, int* slabs, int* tiles_per_slab) {
+    if (N < 1 || rows < 1 || rows > 2147483647ll || D < 1 || D > GMMVI_MAX_DIM_DIAG || capacity < 1 || chunks_requested < 0 ||
+        !chunks || !rows_per_chunk || !slabs || !tiles_per_slab)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_data_tape_plan needs N >= 1, 1 <= rows < 2^31, "
+                                                  "1 <= D <= " + std::to_string(GMMVI_MAX_DIM_DIAG) + ", capacity >= 1, "
+                                                  "chunks_requested >= 0 and four outputs");
+    const size_t budget = scratch_bytes ? scratch_bytes : (size_t)GMMVI_CUSTOM_TAPE_SCRATCH_BYTES;
+    const size_t wave = data_tape_wave_bytes(D, capacity);
+    const int64_t fit = (int64_t)(budget / wave);                    // waves the budget holds
+    if (fit < 1)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "invalid argument: a tape of " + std::to_string(capacity) + " records per lane and "
+                                                      "the gradient accumulator at D = " + std::to_string(D) + " take " +
+                                                      std::to_string(wave) + " bytes for 64 lanes, the scratch budget is " +
+                                                      std::to_string(budget) + " bytes");
+    const int64_t tiles = ((int64_t)N + 63) / 64;
+    int64_t want = chunks_requested;
+    if (want == 0) {
+        const int64_t fill = (GMMVI_DATA_TAPE_PLAN_WAVES + tiles - 1) / tiles;
+        const int64_t most = rows / GMMVI_DATA_TAPE_MIN_CHUNK_ROWS;
+        want = fill < most ? fill : most;
+    }
+    if (want > rows) want = rows;
+    if (want > GMMVI_DATA_MAX_CHUNKS) want = GMMVI_DATA_MAX_CHUNKS;
+    if (want > fit) want = fit;
+    if (want < 1) want = 1;
+    const int64_t per = (rows + want - 1) / want;
+    const int64_t count = (rows + per - 1) / per;
+    const int64_t hold = fit / count < tiles ? fit / count : tiles;  // tiles a slab can hold, >= 1
+    const int64_t need = (tiles + hold - 1) / hold;
+    const int64_t each = (tiles + need - 1) / need;
+    *chunks = (int)count;
+    *rows_per_chunk = (int)per;
+    *tiles_per_slab = (int)each;
+    *slabs = (int)((tiles + each - 1) / each);
+    return GMMVI_OK;
+}
+
+extern "C" int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                             const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
+                                             uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                             int chunks_requested, int tape_capacity, size_t scratch_bytes) {
+    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
+    GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
+    if (t->mode != MODE_DATA_TAPE)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_data_tape needs a target compiled by "
+                                              "gmmvi_custom_target_compile_data_tape; gmmvi_target_custom, gmmvi_target_custom_data "
+                                              "and gmmvi_target_custom_tape launch the other kinds");
+    const int rc = check_data_arguments(ctx, D, data_dev, T, C, minibatch, B, X_dev, N, lp_out_dev, chunks_requested);
+    if (rc != GMMVI_OK) return rc;
+    GMMVI_ARG_CHECK(ctx, tape_capacity >= 0);
+    if (!grad_out_dev)                                               // the data mode's value call: its kernels, its plan, its bits
+        return launch_data(ctx, t, D, params_dev, data_dev, T, C, minibatch, B, seed, call, X_dev, N, lp_out_dev, nullptr,
+                           chunks_requested);
+    const size_t budget = scratch_bytes ? scratch_bytes : (size_t)GMMVI_CUSTOM_TAPE_SCRATCH_BYTES;
+    // the longest tape 64 lanes can have within the budget, beside their accumulator
+    size_t longest = budget / 64 > 4 * (size_t)D ? (budget / 64 - 4 * (size_t)D) / GMMVI_CUSTOM_TAPE_RECORD_BYTES : 0;
+    if (longest > (size_t)1 << 30) longest = (size_t)1 << 30;        // node ids are ints: D + record
+    if (longest < 1)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: a scratch budget of " + std::to_string(budget) +
+                                                  " bytes holds no tape at D = " + std::to_string(D) + ": one record and the gradient "
+                                                  "accumulator of 64 lanes take " + std::to_string(data_tape_wave_bytes(D, 1)) +
+                                                  " bytes");
+    int cap = tape_capacity > 0 ? tape_capacity : tape_length(t, D);
+    if (cap < 1) cap = GMMVI_CUSTOM_TAPE_DEFAULT_CAPACITY;
+    if ((size_t)cap > longest) cap = (int)longest;                   // the launch tells what is needed: refused below if that is more
+    const int64_t length = minibatch ? B : T;
+    RowList l{C, (unsigned)T, minibatch, (unsigned)length, 0u, call, gmmvi_feistel_half_bits((uint32_t)T), (unsigned)seed,
+              (unsigned)(seed >> 32)};
+    float scale = minibatch ? (float)T / (float)B : 1.f;
+    for (int attempt = 0; attempt < 2; ++attempt) {
+        int chunks = 0, per = 0, slabs = 0, tiles_per_slab = 0;
+        if (gmmvi_custom_data_tape_plan(N, length, D, cap, chunks_requested, budget, &chunks, &per, &slabs, &tiles_per_slab) != GMMVI_OK)
+            return gmmvi_fail(ctx, GMMVI_ERR_ARG, g_gmmvi_global_err);
+        l.rows_per_chunk = (unsigned)per;
+        // scratch: [needed length, padded to 256 B | records [waves][cap][64] | adjoints, the same shape | accumulators [waves][D][64]]
+        const size_t waves = (size_t)tiles_per_slab * (size_t)chunks;
+        const size_t f_rec = waves * 64 * (size_t)cap;
+        const int rc2 = gmmvi_ws_reserve(ctx, 256 + waves * data_tape_wave_bytes(D, cap));
+        if (rc2 != GMMVI_OK) return rc2;
+        int* needed_dev = (int*)ctx->ws;
+        char* rec = (char*)ctx->ws + 256;
+        float* adj = (float*)(rec + f_rec * 16);
+        float* acc = adj + f_rec;
+        GMMVI_HIP_CHECK(ctx, hipMemsetAsync(needed_dev, 0, sizeof(int), ctx->stream));
+        const int tiles = (N + 63) / 64;
+        for (int s = 0; s < slabs; ++s) {
+            int first_tile = s * tiles_per_slab;
+            const unsigned here = (unsigned)(tiles - first_tile < tiles_per_slab ? tiles - first_tile : tiles_per_slab);
+            {
+                void* args[] = {&D, &params_dev, &X_dev, &N, &data_dev, &l, &first_tile, &rec, &adj, &acc, &cap, &needed_dev};
+                GMMVI_PROF(ctx, "target_custom_data_tape");
+                GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[6], here, (unsigned)chunks, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
+            }
+            {
+                void* args[] = {&D, &params_dev, &X_dev, &N, &chunks, &scale, &first_tile, &rec, &adj, &acc, &cap, &needed_dev,
+                                &lp_out_dev, &grad_out_dev};
+                GMMVI_PROF(ctx, "target_custom_data_tape_finish");
+                GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[7], here, 1, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
+            }
+        }
+        int needed = 0;
+        GMMVI_HIP_CHECK(ctx, hipMemcpyAsync(&needed, needed_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        GMMVI_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+        if (needed < 1) needed = 1;                                  // constants alone: one slot still carries the chunk's value
+        bool known = false;
+        for (auto& e : t->tape_lengths)
+            if (e.first == D) { known = true; if (needed > e.second) e.second = needed; }
+        if (!known) t->tape_lengths.emplace_back(D, needed);
+        if (needed <= cap) return GMMVI_OK;
+        if ((size_t)needed > longest)
+            return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the target needs a tape of " + std::to_string(needed) +
+                                                      " records per lane at D = " + std::to_string(D) + ", which takes " +
+                                                      std::to_string(data_tape_wave_bytes(D, needed)) + " bytes for 64 lanes with "
+                                                      "their gradient accumulator; the scratch budget is " + std::to_string(budget) +
+                                                      " bytes (lp_out_dev is written, grad_out_dev is not complete)");
+        cap = needed;
+    }
+    return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the tape of the target grew between two launches on the same samples and "
+                                          "rows: gmmvi_user_row or gmmvi_user_prior is not a pure function of x, D, the row and params");
 }

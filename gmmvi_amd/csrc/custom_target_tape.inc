@@ -195,8 +195,11 @@ struct Input {
 
 }  // namespace gmmvi_tape
 
-// (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there)
+// (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there;
+// behind the dual-number text, which defines it too, GMMVI_TAPE_NO_FLOAT_VALUE leaves it out)
+#ifndef GMMVI_TAPE_NO_FLOAT_VALUE
 __host__ __device__ inline float gmmvi_value(float a) { return a; }
+#endif
 
 #ifndef GMMVI_TAPE_NO_KERNELS
 // Value call: one float instantiation per sample, no tape.

@@ -128,6 +128,27 @@ def custom_target_check_tape(source, arch="gfx950"):
     return int(rc), log.value.decode(errors="replace")
 
 
+def custom_target_check_data_tape(source, arch="gfx950"):
+    """custom_target_check for a source that defines ``gmmvi_user_row`` and ``gmmvi_user_prior``, compiled for the data mode with
+    reverse-mode gradients (csrc/custom_target_data_tape.inc).  -> (status, compiler log)."""
+    import ctypes as C
+    log = C.create_string_buffer(1 << 16)
+    rc = _lib.load().gmmvi_custom_target_check_data_tape(str(source).encode(), str(arch).encode(), log, len(log))
+    return int(rc), log.value.decode(errors="replace")
+
+
+def custom_data_tape_plan(n, rows, d, capacity, chunks_requested=0, scratch_bytes=0):
+    """The plan of a gradient call of ``target_custom_data_tape`` for n samples and a row list of ``rows`` at dimension d and
+    ``capacity`` records per lane within ``scratch_bytes`` (0: the default budget) (gmmvi_custom_data_tape_plan; needs no device)
+    -> (chunks, rows_per_chunk, slabs, tiles_per_slab)."""
+    import ctypes as C
+    out = [C.c_int() for _ in range(4)]
+    lib = _lib.load()
+    _lib.check(None, lib.gmmvi_custom_data_tape_plan(int(n), int(rows), int(d), int(capacity), int(chunks_requested),
+                                                     int(scratch_bytes), *[C.byref(o) for o in out]))
+    return tuple(o.value for o in out)
+
+
 def custom_tape_plan(n, capacity, scratch_bytes=0):
     """The slab plan of a tape-mode gradient call on n samples at ``capacity`` records per lane within ``scratch_bytes`` (0: the
     default budget) (gmmvi_custom_tape_plan; needs no device) -> (slabs, lanes_per_slab)."""
@@ -167,14 +188,15 @@ class CustomTarget:
             pass
 
 
-CUSTOM_TARGET_MODES = ("hand", "autodiff", "data", "tape")
+CUSTOM_TARGET_MODES = ("hand", "autodiff", "data", "tape", "data_tape")
 
 
 def custom_target_compile(ctx, source, autodiff=False, mode=None):
     """Compiles ``source`` (the contract: include/gmmvi_hip.h) for the context's device -> CustomTarget.  mode: "hand" (the
     source defines ``gmmvi_user_target``), "autodiff" (``gmmvi_user_density``, the library differentiates it) or "data"
     (``gmmvi_user_row`` and ``gmmvi_user_prior``, launched by ``target_custom_data``) or "tape" (``gmmvi_user_density``,
-    differentiated in reverse mode, launched by ``target_custom_tape``); None: ``autodiff`` chooses between the first two.  A source that does not compile raises GmmviError with the compiler log."""
+    differentiated in reverse mode, launched by ``target_custom_tape``) or "data_tape" (the source of "data", its gradient in
+    reverse mode, launched by ``target_custom_data_tape``); None: ``autodiff`` chooses between the first two.  A source that does not compile raises GmmviError with the compiler log."""
     import ctypes as C
     if mode is None:
         mode = "autodiff" if autodiff else "hand"
@@ -182,7 +204,8 @@ def custom_target_compile(ctx, source, autodiff=False, mode=None):
         raise ValueError(f"mode: expected one of {CUSTOM_TARGET_MODES}, got {mode!r}")
     h = C.c_void_p()
     compile_fn = {"hand": ctx.lib.gmmvi_custom_target_compile, "autodiff": ctx.lib.gmmvi_custom_target_compile_autodiff,
-                  "data": ctx.lib.gmmvi_custom_target_compile_data, "tape": ctx.lib.gmmvi_custom_target_compile_tape}[mode]
+                  "data": ctx.lib.gmmvi_custom_target_compile_data, "tape": ctx.lib.gmmvi_custom_target_compile_tape,
+                  "data_tape": ctx.lib.gmmvi_custom_target_compile_data_tape}[mode]
     ctx.check(compile_fn(ctx.handle, str(source).encode(), C.byref(h)))
     return CustomTarget(ctx, h)
 
@@ -252,6 +275,35 @@ def target_custom_tape(ctx, handle, params, x, want_grad=True, tape_capacity=0, 
         ctx.check(ctx.lib.gmmvi_target_custom_tape(ctx.handle, handle.handle, d, None if params is None else params.ptr, x.ptr, n,
                                                    lp.ptr, None if grad is None else grad.ptr, int(tape_capacity),
                                                    int(scratch_bytes)))
+    return lp, grad
+
+
+def target_custom_data_tape(ctx, handle, params, data, x, want_grad=True, batch_size=None, seed=0, call=0, chunks=0,
+                            tape_capacity=0, scratch_bytes=0):
+    """``target_custom_data`` for a handle of mode "data_tape": the same target, the same value call, and the gradient from
+    reverse mode on a tape that is reused for every row (csrc/custom_target_data_tape.inc), at any D up to ``_lib.MAX_DIM_DIAG``.
+    tape_capacity: records per lane, 0 what the handle has needed at this D so far; scratch_bytes: the budget of the tapes and
+    accumulators, 0 the default.  A gradient call synchronises the stream.  -> (lp [n], grad [n, D] or None)."""
+    if not isinstance(handle, CustomTarget):
+        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
+    n, d = x.shape
+    _req(x, (n, d), name="x")
+    if len(data.shape) != 2:
+        raise ValueError(f"data: expected a two-dimensional array, got {data.shape}")
+    t, c = data.shape
+    _req(data, (t, c), name="data")
+    if params is not None:
+        if len(params.shape) != 1:
+            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
+        _req(params, params.shape, name="params")
+    lp = ctx.empty((n,))
+    grad = ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        ctx.check(ctx.lib.gmmvi_target_custom_data_tape(
+            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c,
+            0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
+            int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks), int(tape_capacity),
+            int(scratch_bytes)))
     return lp, grad
 
 

@@ -491,6 +491,60 @@ int gmmvi_target_custom_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* target, 
  * unknown op or a NULL output: GMMVI_ERR_ARG. */
 int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb, int* records);
 
+/* ---- targets summed over a data set, differentiated on a tape ------------------------------------------------------------------
+ * The source of the data mode, unchanged (gmmvi_user_row and gmmvi_user_prior, templates over the number type; compiled with
+ * -DGMMVI_CUSTOM_TAPE=1), with the gradient from reverse mode at any D up to GMMVI_MAX_DIM_DIAG: forward mode makes ceil(D / 16)
+ * passes over every row and stops at GMMVI_CUSTOM_AUTODIFF_MAX_DIM.  The library puts the whole text of the data mode, the
+ * tape's number type (csrc/custom_target_tape.inc, same records, partials and tie rules) and csrc/custom_target_data_tape.inc
+ * behind the source.  The key of the module cache is (source, mode): the same text compiled by gmmvi_custom_target_compile_data
+ * gives another handle.
+ * Value call (grad_out_dev == NULL): the value call of gmmvi_target_custom_data, kernel for kernel and bit for bit; no tape, no
+ * synchronisation.
+ * Gradient call: one wave of 64 lanes per (tile of 64 samples, chunk of the row list), lane = sample.  For each row of its chunk
+ * in order the lane resets its record count, records the row term on a tape of `capacity` records that is reused for every
+ * row, adds the value to its sum and walks the records back from the output node into its column of the wave's [D][64] gradient
+ * accumulator in scratch.  The tape is as long as the longest single row term or the prior, not the data sum.  A second kernel,
+ * one wave per tile, adds the chunks' partials, scales, adds the prior and sweeps the prior, recorded on the same tape, into the
+ * scaled accumulator, then writes lp and grad.
+ * Summation order, fixed (no atomic takes part in a floating-point sum; two identical calls give identical bits): per lane the
+ * rows of a chunk in position order, the adjoints of one row from the output's record back to record 0; chunks in index order;
+ * then s * sum; then + prior (value), and the prior's adjoints in sweep order (gradient).
+ * Capacity, as for gmmvi_target_custom_tape: tape_capacity == 0 means what this handle has needed at this D so far (first use:
+ * GMMVI_CUSTOM_TAPE_DEFAULT_CAPACITY); every lane raises an integer maximum of its record counts over all rows and the prior; the
+ * call reads it back (it SYNCHRONISES the stream: modular path only), remembers it (gmmvi_custom_tape_length) and, if it exceeded
+ * the capacity, runs once more at that length with the same seed and call, hence the same rows.  A second overflow is
+ * GMMVI_ERR_ARG (the source is not a pure function).  A lane whose tape overflows still computes values and adds no adjoints.
+ * Scratch: 64 * (capacity * GMMVI_CUSTOM_TAPE_RECORD_BYTES + 4 D) bytes per tile and chunk within scratch_bytes (0:
+ * GMMVI_CUSTOM_TAPE_SCRATCH_BYTES); tiles that do not fit together run in slabs, one after another on the stream.  x is read
+ * from X_dev directly.  gmmvi_target_custom, gmmvi_target_custom_data and gmmvi_target_custom_tape refuse a handle of this mode,
+ * and this entry refuses the other four kinds, with GMMVI_ERR_ARG and a message naming the right entry. */
+int gmmvi_custom_target_check_data_tape(const char* source, const char* arch, char* log_out, size_t log_cap);
+int gmmvi_custom_target_compile_data_tape(gmmvi_ctx* ctx, const char* source, gmmvi_custom_target** out);
+/* The plan of a gradient call on N samples and a row list of `rows` at dimension D and `capacity` records per lane (needs no
+ * device).  Chunks: the request, or (0) enough that tiles * chunks waves reach four per compute unit of an MI355X but no fewer
+ * than 8 rows per chunk unless there is one chunk (set by the rule of gmmvi_custom_data_plan, not measured); at most one per row
+ * and at most what the budget holds.  Then as many tiles per slab as the budget holds.  The last chunk and the last slab are
+ * never empty; chunks * tiles_per_slab waves never exceed the budget.  GMMVI_ERR_ARG: N < 1, rows outside 1 .. 2^31 - 1, D
+ * outside 1 .. GMMVI_MAX_DIM_DIAG, capacity < 1, chunks_requested < 0, a NULL output, or a budget that cannot hold one tile with
+ * one chunk (the message gives both byte counts). */
+int gmmvi_custom_data_tape_plan(int N, int64_t rows, int D, int capacity, int chunks_requested, size_t scratch_bytes, int* chunks,
+                                int* rows_per_chunk, int* slabs, int* tiles_per_slab);
+/* Arguments and refusals of gmmvi_target_custom_data, without its cap on D for a gradient, plus tape_capacity >= 0 and
+ * scratch_bytes as above.  Profiling tags: target_custom_data_tape, target_custom_data_tape_finish (gradient call);
+ * target_custom_data, target_custom_data_merge (value call). */
+int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                                  const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed, uint32_t call,
+                                  const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int chunks_requested,
+                                  int tape_capacity, size_t scratch_bytes);
+/* The two lane bodies of csrc/custom_target_data_tape.inc on the host (no device, no context), lane stride 1, behind the
+ * logistic-regression row term and prior of csrc/custom_data_tape_sample.hip (row = [features (D) | label], params = [prior mean,
+ * prior std]): all arrays are host arrays, the row list is that of gmmvi_target_custom_data for (minibatch, B, seed, call), the
+ * chunk plan is given and must cover the row list with a non-empty last chunk.  Writes lp[N] and *needed, the longest record
+ * count of a row term or the prior; grad[N, D] is written only if *needed <= capacity.  GMMVI_ERR_ARG for a bad argument. */
+int gmmvi_data_tape_probe(int D, const float* params, const float* data, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
+                          uint32_t call, const float* X, int N, int chunks, int rows_per_chunk, int capacity, float* lp,
+                          float* grad, int* needed);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
