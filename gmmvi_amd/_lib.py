@@ -206,6 +206,9 @@ _PROTOS = {
     "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "gmmvi_target_custom_data_tape": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i, _i, _sz]),
     "gmmvi_data_tape_probe": (_i, [_i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _i, _i, _i, _p, _p, C.POINTER(_i)]),
+    "gmmvi_custom_data_predictive_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64)]),
+    "gmmvi_custom_data_predictive": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _p, _i, _p, _p, _p, _i]),
+    "gmmvi_custom_data_predictive_probe": (_i, [_p, _i, C.c_int64, _i, _p, _p, _p]),
     "gmmvi_sample_components": (_i, [_p, _i, _i, _p, _p, _p, _i, _u64, _u64, _i, _p, _p, _p]),
     "gmmvi_philox_normals": (_i, [_p, _u64, _u64, _i, _i, _i, _p]),
     "gmmvi_philox_uniforms": (_i, [_p, _u64, _u64, _i, _i, _p]),

@@ -1,7 +1,8 @@
 // Build-time check of the kernels of user-defined targets summed over a data set (custom_target_data.inc): the Makefile compiles
 // that text behind this small row term and prior, with the dual-number text (no adapter), the tile mover of the wrapper text
 // and the Feistel stream in front of it, as custom_target.hip composes them at run time and with the flags of the library.  A
-// mistake in the text fails the build, and the register / scratch / LDS use of the six kernels on gfx950 can be read from
+// mistake in the text fails the build, and the register / scratch / LDS use of the nine kernels (the six of the target, the three
+// of its predictive density) on gfx950 can be read from
 // build/custom_data_sample.s (kernel table).  Nothing of this file is linked into the library.
 #include <hip/hip_runtime.h>
 #include "gmmvi_hip.h"

@@ -7,7 +7,8 @@
 // Targets summed over a data set (gmmvi_custom_target_compile_data): the user's source defines gmmvi_user_row and
 // gmmvi_user_prior; behind it go the dual-number text without its adapter, the tile mover of the wrapper text, the Feistel
 // stream (feistel.h and philox.h, made one string by the Makefile) and the kernels of custom_target_data.inc, which
-// gmmvi_target_custom_data launches.
+// gmmvi_target_custom_data launches.  The same text ends with the predictive kernels (the reduction over the samples of the row
+// terms on an evaluation set), which gmmvi_custom_data_predictive launches for a handle of either data mode.
 // Targets differentiated on a tape (gmmvi_custom_target_compile_tape): the source of the differentiated mode, unchanged; behind it
 // goes custom_target_tape.inc alone, the tape's number type and its two kernels, which gmmvi_target_custom_tape launches.
 // Targets summed over a data set and differentiated on a tape (gmmvi_custom_target_compile_data_tape): the source of the data
@@ -153,8 +154,9 @@ struct gmmvi_custom_target {
     Mode mode = MODE_HAND;
     int refs = 0;
     hipModule_t module = nullptr;
-    hipFunction_t fn[8] = {};              // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
-                                           // MODE_TAPE: lp, lp + grad; MODE_DATA_TAPE: the six of MODE_DATA, tape rows, tape finish
+    hipFunction_t fn[11] = {};             // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
+                                           // MODE_TAPE: lp, lp + grad; MODE_DATA_TAPE: the six of MODE_DATA, tape rows, tape finish;
+                                           // both data modes: fn[8 .. 10] predictive staged, direct, merge
     mutable std::vector<std::pair<int, int>> tape_lengths;   // the tape modes: (D, the longest tape a gradient launch at that D has needed)
 };
 
@@ -236,6 +238,10 @@ static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_c
     hipError_t e = hipSetDevice(ctx->device);
     if (e == hipSuccess) e = hipModuleLoadData(&t->module, code.data());
     for (int i = 0; e == hipSuccess && i < count; ++i) e = hipModuleGetFunction(&t->fn[i], t->module, names[i]);
+    static const char* const predictive_names[3] = {"gmmvi_data_predictive_staged", "gmmvi_data_predictive_direct",
+                                                    "gmmvi_data_predictive_merge"};
+    for (int i = 0; e == hipSuccess && i < 3 && (mode == MODE_DATA || mode == MODE_DATA_TAPE); ++i)
+        e = hipModuleGetFunction(&t->fn[8 + i], t->module, predictive_names[i]);
     if (e != hipSuccess) {
         if (t->module) (void)hipModuleUnload(t->module);
         delete t;
@@ -440,6 +446,71 @@ extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_targe
                                                   " (a value call runs above)");
     return launch_data(ctx, t, D, params_dev, data_dev, T, C, minibatch, B, seed, call, X_dev, N, lp_out_dev, grad_out_dev,
                        chunks_requested);
+}
+
+// ---- predictive density of a data-set target: the reduction over the samples -------------------------------------------------------
+extern "C" int gmmvi_custom_data_predictive_plan(int N, int64_t M, int chunks_requested, int* tiles, int* chunks,
+                                                 int64_t* rows_per_chunk) {
+    if (N < 1 || M < 1 || M > 2147483647ll || chunks_requested < 0 || !tiles || !chunks || !rows_per_chunk)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_data_predictive_plan needs N >= 1, 1 <= M < 2^31, "
+                                                  "chunks_requested >= 0 and three outputs");
+    int count = 0, per = 0;
+    const int rc = gmmvi_custom_data_plan(N, M, chunks_requested, &count, &per);
+    if (rc != GMMVI_OK) return rc;
+    *tiles = (int)(((int64_t)N + 63) / 64);
+    *chunks = count;
+    *rows_per_chunk = per;
+    return GMMVI_OK;
+}
+
+extern "C" int gmmvi_custom_data_predictive(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                            const float* rows_dev, int64_t M, int C, const float* X_dev, int N, float* lpd_out_dev,
+                                            float* mean_out_dev, float* var_out_dev, int chunks_requested) {
+    GMMVI_ARG_CHECK(ctx, ctx != nullptr);
+    if (!t || !rows_dev || !X_dev || !lpd_out_dev)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_data_predictive needs a target handle, rows_dev, X_dev "
+                                              "and lpd_out_dev (only mean_out_dev and var_out_dev may be NULL)");
+    if (find_target(ctx, t) == ctx->custom_targets.end())
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the custom target does not belong to this context");
+    if (t->mode != MODE_DATA && t->mode != MODE_DATA_TAPE)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_custom_data_predictive needs a target compiled by "
+                                              "gmmvi_custom_target_compile_data or gmmvi_custom_target_compile_data_tape (a row term "
+                                              "to evaluate on held-out rows); this handle has none");
+    if (N < 1) return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the predictive density needs N >= 1 samples, got N = " + std::to_string(N));
+    if (M < 1 || M > 2147483647ll)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the evaluation set needs 1 <= M < 2^31 rows, got M = " + std::to_string(M));
+    if (C < 1)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: a data row needs C >= 1 floats, got C = " + std::to_string(C));
+    if (D < 1 || D > GMMVI_MAX_DIM_DIAG)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the predictive density needs 1 <= D <= " +
+                                                  std::to_string(GMMVI_MAX_DIM_DIAG) + ", got D = " + std::to_string(D));
+    GMMVI_ARG_CHECK(ctx, chunks_requested >= 0);
+    int tiles = 0, chunks = 0;
+    int64_t per64 = 0;
+    if (gmmvi_custom_data_predictive_plan(N, M, chunks_requested, &tiles, &chunks, &per64) != GMMVI_OK)
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, g_gmmvi_global_err);
+    float* part = nullptr;
+    if (tiles > 1) {                                                 // [tiles][M] partials of (max, sumexp, mean, M2)
+        const int rc = gmmvi_ws_reserve(ctx, (size_t)tiles * (size_t)M * 4 * sizeof(float));
+        if (rc != GMMVI_OK) return rc;
+        part = (float*)ctx->ws;
+    }
+    const bool staged = D <= GMMVI_CUSTOM_STAGED_MAX_DIM;
+    const size_t lds = staged ? (size_t)64 * (D | 1) * sizeof(float) : 0;   // the x image [64][D | 1]: 30976 B at D = 120
+    unsigned rows = (unsigned)M, per = (unsigned)per64;
+    {
+        void* args[] = {&D, &params_dev, &X_dev, &N, &rows_dev, &rows, &C, &per, &part, &lpd_out_dev, &mean_out_dev, &var_out_dev};
+        GMMVI_PROF(ctx, "custom_data_predictive");
+        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[staged ? 8 : 9], (unsigned)tiles, (unsigned)chunks, 1, 256, 1, 1, (unsigned)lds,
+                                                   ctx->stream, args, nullptr));
+    }
+    if (tiles > 1) {
+        const size_t blocks = ((size_t)M + 255) / 256;
+        void* args[] = {&N, &rows, &tiles, &part, &lpd_out_dev, &mean_out_dev, &var_out_dev};
+        GMMVI_PROF(ctx, "custom_data_predictive_merge");
+        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[10], (unsigned)blocks, 1, 1, 256, 1, 1, 0, ctx->stream, args, nullptr));
+    }
+    return GMMVI_OK;
 }
 
 // ---- targets differentiated on a tape ----------------------------------------------------------------------------------------

@@ -202,4 +202,167 @@ extern "C" __global__ __launch_bounds__(256) void gmmvi_data_merge_grad(int D, c
                                                                          const float* part_grad) {
     gmmvi_data::merge<true>(D, params, X, N, chunks, scale, lp, grad, part_lp, part_grad);
 }
+
+// ---- held-out predictive density: the reduction over the SAMPLES (gmmvi_custom_data_predictive; contract: include/gmmvi_hip.h,
+// "predictive density of a data-set target") ---------------------------------------------------------------------------------------
+// l[n, m] = gmmvi_user_row<float>(x_n, D, rows[m], C, params) for an evaluation set rows[M, C]; the prior takes no part.  Per row:
+//     lpd[m] = log sum_n exp(l[n, m]) - log N (max-shifted),  mean[m] = sum_n l[n, m] / N,  var[m] = M2 / (N - 1) (0 for N = 1).
+// gmmvi_data_predictive_*: the geometry of gmmvi_data_rows_*: grid (ceil(N / 64), chunks of the evaluation rows), 4 waves on the
+// same 64 samples, lane = sample, wave w on positions w, w + 4, ... of its chunk, the row wave-uniform.  For its row the wave
+// reduces over its lanes with an xor butterfly (1, 2, ..., 32; every lane ends with the same bits): the maximum, the sum of
+// exp(l - shift), the sum of l (hence the tile mean), the sum of (l - tile mean)^2.  Lanes past N take no part: -inf to the
+// maximum, 0 to the sums, and the tile's count is the number of valid lanes.  Lane 0 writes the tile's partial (max, sumexp, mean,
+// M2) as one 16-byte vector store to part[tile][row], or, with one tile, finishes the row in place.
+// gmmvi_data_predictive_merge: thread = row; merges the tiles IN TILE-INDEX ORDER: the log-sum-exp pairs by rescaling to the
+// running maximum, mean and M2 by the pairwise update.  No atomics; chunks split the rows only, never a reduction, so a chunk
+// request changes no output bit.
+// Edge values: shift = the maximum if it is finite, else 0, so a column of -inf gives sumexp = 0 and lpd = -inf with no
+// -inf - (-inf); +inf gives +inf; fmaxf drops a NaN, the sum of exponentials carries it into lpd.  A partial whose sumexp is
+// exactly 0 (all -inf) is not rescaled (0 * exp(+large) would be NaN).  mean and var of a column that holds a non-finite value
+// are whatever IEEE arithmetic gives.
+// The functions between the two marker lines are __host__ __device__ over the lane type V: float on the device (one lane of a
+// wave), a 64-wide vector in the host probe (csrc/predictive_probe.hip), which the Makefile feeds with exactly these lines.
+// GMMVI_PRED_COMBINE_BEGIN
+namespace gmmvi_pred {
+
+struct Part { float max, sumexp, mean, m2; };
+
+// one lane's side of the wave operations; the host probe defines the same five for its vector type
+__device__ __forceinline__ float lane_xor(float v, int mask) { return __shfl_xor(v, mask, 64); }
+__device__ __forceinline__ float lane_max(float a, float b) { return fmaxf(a, b); }
+__device__ __forceinline__ float lane_exp(float v) { return expf(v); }
+__device__ __forceinline__ float lane_pick(bool c, float a, float b) { return c ? a : b; }
+__device__ __forceinline__ float lane_first(float v) { return v; }
+
+template <class V>
+__host__ __device__ inline V wave_max(V v) {
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) v = lane_max(v, lane_xor(v, mask));
+    return v;
+}
+template <class V>
+__host__ __device__ inline V wave_sum(V v) {
+#pragma unroll
+    for (int mask = 1; mask < 64; mask <<= 1) v = v + lane_xor(v, mask);
+    return v;
+}
+
+__host__ __device__ inline float shift_of(float mx) { return __builtin_isfinite(mx) ? mx : 0.f; }
+
+// the partial of one tile for one row: l is the lane's row term, valid whether the lane is a sample, count the valid lanes
+template <class V, class B>
+__host__ __device__ inline Part tile_reduce(const V& l, const B& valid, int count) {
+    Part p;
+    p.max = lane_first(wave_max(lane_pick(valid, l, V(-__builtin_huge_valf()))));
+    const float shift = shift_of(p.max);
+    p.sumexp = lane_first(wave_sum(lane_pick(valid, lane_exp(l - V(shift)), V(0.f))));
+    p.mean = lane_first(wave_sum(lane_pick(valid, l, V(0.f)))) / (float)count;
+    const V d = l - V(p.mean);
+    p.m2 = lane_first(wave_sum(lane_pick(valid, d * d, V(0.f))));
+    return p;
+}
+
+// puts the partial t of c samples behind the running partial of n samples
+__host__ __device__ inline void merge_part(Part& run, int n, const Part& t, int c) {
+    const float mx = fmaxf(run.max, t.max);
+    const float shift = shift_of(mx);
+    const float a = run.sumexp == 0.f ? 0.f : run.sumexp * expf(shift_of(run.max) - shift);
+    const float b = t.sumexp == 0.f ? 0.f : t.sumexp * expf(shift_of(t.max) - shift);
+    run.max = mx;
+    run.sumexp = a + b;
+    const float total = (float)(n + c);
+    const float delta = t.mean - run.mean;
+    run.mean += delta * (float)c / total;
+    run.m2 += t.m2 + delta * delta * (float)n * (float)c / total;
+}
+
+__host__ __device__ inline void finish_part(const Part& p, int N, float& lpd, float& mean, float& var) {
+    lpd = (shift_of(p.max) + logf(p.sumexp)) - logf((float)N);
+    mean = p.mean;
+    var = N > 1 ? p.m2 / (float)(N - 1) : 0.f;
+}
+
+}  // namespace gmmvi_pred
+// GMMVI_PRED_COMBINE_END
+
+namespace gmmvi_data {
+
+template <bool STAGED>
+__device__ __forceinline__ void predictive(int D, const float* params, const float* X, int N, const float* rows, unsigned M, int C,
+                                           unsigned rows_per_chunk, float* part, float* lpd, float* mean, float* var) {
+    extern __shared__ float gmmvi_pred_lds[];
+    const int lane = threadIdx.x & 63;
+    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int S = D | 1;
+    const size_t n0 = (size_t)blockIdx.x * 64;
+    const int valid = (size_t)N - n0 < 64 ? (int)((size_t)N - n0) : 64;
+    const int mine = lane < valid ? lane : valid - 1;     // lanes past N read the tile's last sample and are masked out below
+    const float* x;
+    if (STAGED) {
+        float* xs = gmmvi_pred_lds;
+        const int r0 = 16 * w;                            // wave w moves rows 16 w .. 16 w + 15 of the tile
+        const int count = valid - r0 < 16 ? valid - r0 : 16;
+        if (count > 0)
+            gmmvi_wrap::move_tile<true>(const_cast<float*>(X) + (n0 + r0) * (size_t)D, xs + r0 * S, D, S, count * D, lane);
+        __syncthreads();
+        x = xs + mine * S;
+    } else {
+        x = X + (n0 + mine) * (size_t)D;
+    }
+    const unsigned begin = blockIdx.y * rows_per_chunk;
+    const unsigned end = M - begin < rows_per_chunk ? M : begin + rows_per_chunk;
+    const bool single = gridDim.x == 1;
+    for (unsigned p = begin + w; p < end; p += 4) {
+        const unsigned m = (unsigned)__builtin_amdgcn_readfirstlane((int)p);
+        const float l = gmmvi_user_row<float, const float*>(x, D, rows + (size_t)m * (size_t)C, C, params);
+        const gmmvi_pred::Part t = gmmvi_pred::tile_reduce(l, lane < valid, valid);
+        if (lane == 0) {
+            if (single) {
+                float a, b, c;
+                gmmvi_pred::finish_part(t, N, a, b, c);
+                lpd[m] = a;
+                if (mean) mean[m] = b;
+                if (var) var[m] = c;
+            } else {
+                reinterpret_cast<float4*>(part)[(size_t)blockIdx.x * (size_t)M + m] = make_float4(t.max, t.sumexp, t.mean, t.m2);
+            }
+        }
+    }
+}
+
+}  // namespace gmmvi_data
+
+#define GMMVI_DATA_PREDICTIVE_KERNEL(name, STAGED)                                                                          \
+    extern "C" __global__ __launch_bounds__(256) void name(int D, const float* __restrict__ params,                         \
+                                                           const float* __restrict__ X, int N,                             \
+                                                           const float* __restrict__ rows, unsigned M, int C,              \
+                                                           unsigned rows_per_chunk, float* part, float* lpd, float* mean,  \
+                                                           float* var) {                                                   \
+        gmmvi_data::predictive<STAGED>(D, params, X, N, rows, M, C, rows_per_chunk, part, lpd, mean, var);                 \
+    }
+GMMVI_DATA_PREDICTIVE_KERNEL(gmmvi_data_predictive_staged, true)
+GMMVI_DATA_PREDICTIVE_KERNEL(gmmvi_data_predictive_direct, false)
+#undef GMMVI_DATA_PREDICTIVE_KERNEL
+
+// tiles > 1: the thread is the row; merges the tiles' partials in tile-index order and finishes the row
+extern "C" __global__ __launch_bounds__(256) void gmmvi_data_predictive_merge(int N, unsigned M, int tiles, const float* part,
+                                                                               float* lpd, float* mean, float* var) {
+    const size_t m = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (m >= (size_t)M) return;
+    const float4* p4 = reinterpret_cast<const float4*>(part);
+    float4 q = p4[m];
+    gmmvi_pred::Part run{q.x, q.y, q.z, q.w};
+    int n = N < 64 ? N : 64;
+    for (int t = 1; t < tiles; ++t) {
+        const int c = N - 64 * t < 64 ? N - 64 * t : 64;
+        q = p4[(size_t)t * (size_t)M + m];
+        gmmvi_pred::merge_part(run, n, gmmvi_pred::Part{q.x, q.y, q.z, q.w}, c);
+        n += c;
+    }
+    float a, b, c;
+    gmmvi_pred::finish_part(run, N, a, b, c);
+    lpd[m] = a;
+    if (mean) mean[m] = b;
+    if (var) var[m] = c;
+}
 )GMMVI_DATA"

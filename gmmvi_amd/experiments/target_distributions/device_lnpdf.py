@@ -173,7 +173,16 @@ class _DeviceDataTarget(MinibatchLNPDF):
     def _target_call(self, x, want_grad, batch_size, call):
         raise NotImplementedError
 
-    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0):
+    @staticmethod
+    def _host_rows(rows, columns, name):
+        """``rows`` as a contiguous fp32 host array [M >= 1, columns], or ValueError; touches no device."""
+        rows = np.ascontiguousarray(np.asarray(rows.numpy() if hasattr(rows, "numpy") else rows), np.float32)
+        if rows.ndim != 2 or rows.shape[0] < 1 or rows.shape[1] != columns:
+            raise ValueError(f"{name} must be two-dimensional [rows >= 1, {columns}] (the columns of the training data), got shape "
+                             f"{rows.shape}")
+        return rows
+
+    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, eval_sets=None, report_waic=False):
         super().__init__(seed)
         if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
             raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
@@ -187,8 +196,15 @@ class _DeviceDataTarget(MinibatchLNPDF):
             params = np.ascontiguousarray(np.asarray(params.numpy() if hasattr(params, "numpy") else params), np.float32)
             if params.ndim != 1:
                 raise ValueError(f"params must be one-dimensional, got shape {params.shape}")
+        if eval_sets is not None:
+            if not isinstance(eval_sets, dict):
+                raise ValueError(f"eval_sets must be a dict name -> [rows, {data.shape[1]}] array or None, got {type(eval_sets)}")
+            eval_sets = {str(name): self._host_rows(rows, data.shape[1], f"eval_sets[{name!r}]") for name, rows in eval_sets.items()}
         self.ctx = get_context()
         self.source = str(source)
+        self.report_waic = bool(report_waic)
+        self._data_columns = int(data.shape[1])
+        self._eval_sets_dev = {} if eval_sets is None else {name: self.ctx.asarray(rows) for name, rows in eval_sets.items()}
         self.batch_size = None if batch_size is None else int(batch_size)
         self.num_data = int(data.shape[0])
         self._num_dimensions = int(num_dimensions)
@@ -217,9 +233,44 @@ class _DeviceDataTarget(MinibatchLNPDF):
         """The full-data log density (all rows in index order, s = 1) of a minibatch target; the call counter stays."""
         return self._target_call(self._x(x), False, None, 0)[0]
 
+    def log_predictive(self, samples, rows=None):
+        """Per row of ``rows`` [M, C] (None: the training data on the device) over the samples [N, D]: ``lpd`` = log (1/N) sum_n
+        p(row | x_n), ``mean`` = the mean and ``var`` = the unbiased variance over the samples of log p(row | x_n); the prior
+        takes no part (csrc/custom_target_data.inc, one reduction over the samples on the device).  -> (lpd, mean, var), device
+        arrays of length M.  The call counter of a minibatch target stays."""
+        if rows is not None:
+            rows = self._host_rows(rows, self._data_columns, "rows")
+        x = self._x(samples)
+        if x.shape[0] < 1:
+            raise ValueError("log_predictive needs at least one sample")
+        rows_dev = self._data_dev if rows is None else self.ctx.asarray(rows)
+        return hip_ops.custom_data_predictive(self.ctx, self._handle, self._params_dev, rows_dev, x)
+
+    def waic(self, samples):
+        """WAIC over the training rows: ``lppd`` = sum_m lpd[m], ``p_waic`` = sum_m var[m] and ``elpd_waic`` = lppd - p_waic of
+        ``log_predictive(samples)``; the sums over the rows are taken in fp64 on the host."""
+        lpd, _, var = self.log_predictive(samples)
+        lppd = float(np.sum(lpd.numpy(), dtype=np.float64))
+        p_waic = float(np.sum(var.numpy(), dtype=np.float64))
+        return {"lppd": lppd, "p_waic": p_waic, "elpd_waic": lppd - p_waic}
+
+    def expensive_metrics(self, model, samples) -> dict:
+        """Per evaluation set of ``eval_sets``: ``{name}_lpd``, the mean over its rows of the log posterior-predictive density,
+        and ``{name}_mean_ll``, the mean over rows and samples of the row's log-likelihood; with ``report_waic`` also ``lppd``,
+        ``p_waic`` and ``elpd_waic`` of the training rows.  Neither keyword given: the empty dict of ``LNPDF``."""
+        metrics = dict()
+        for name, rows_dev in self._eval_sets_dev.items():
+            lpd, mean, _ = hip_ops.custom_data_predictive(self.ctx, self._handle, self._params_dev, rows_dev, self._x(samples))
+            metrics[f"{name}_lpd"] = float(np.mean(lpd.numpy(), dtype=np.float64))
+            metrics[f"{name}_mean_ll"] = float(np.mean(mean.numpy(), dtype=np.float64))
+        if self.report_waic:
+            metrics.update(self.waic(samples))
+        return metrics
+
 
 class DeviceDataLNPDF(_DeviceDataTarget):
-    """``DeviceDataLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0)``: ``source`` defines
+    """``DeviceDataLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0, eval_sets=None,
+    report_waic=False)``: ``source`` defines
     ``gmmvi_user_row`` and ``gmmvi_user_prior`` (contract: include/gmmvi_hip.h), ``data`` is the 2-D data set, uploaded once as
     fp32, and the target is ``prior(x) + s * sum_r row(x, data[r])``.
 
@@ -229,7 +280,10 @@ class DeviceDataLNPDF(_DeviceDataTarget):
     ``log_density_full(x)`` is then the full-data value in index order, counter untouched.
     The gradient comes from the library's dual numbers (num_dimensions <= _lib.CUSTOM_AUTODIFF_MAX_DIM) and is computed only
     for an estimator that reads it.  There is no ``_fast_path_target``: the iteration runs module by module, as for the other
-    minibatch targets."""
+    minibatch targets.
+    eval_sets: a dict name -> [M, C] array of held-out rows with the columns of ``data``, uploaded once; ``expensive_metrics``
+    then reports ``{name}_lpd`` and ``{name}_mean_ll`` for each, and with report_waic=True the WAIC of the training rows
+    (``log_predictive``, ``waic``)."""
 
     _mode = "data"
 
@@ -246,7 +300,7 @@ class DeviceDataLNPDF(_DeviceDataTarget):
 
 class DeviceDataTapeLNPDF(_DeviceDataTarget):
     """``DeviceDataTapeLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0, tape_capacity=None,
-    scratch_bytes=None)``: the source, the data, the minibatches, the call counter and the values of a ``DeviceDataLNPDF``, with
+    scratch_bytes=None, eval_sets=None, report_waic=False)``: the source, the data, the minibatches, the call counter and the values of a ``DeviceDataLNPDF``, with
     the gradient from reverse mode (csrc/custom_target_data_tape.inc): every sample records one row's term at a time on a short
     tape in device scratch, reused for every row, and walks it back into a gradient accumulator.  The cost per row does not grow
     with ``ceil(D / 16)``, and ``num_dimensions`` goes up to ``_lib.MAX_DIM_DIAG``.
@@ -259,17 +313,18 @@ class DeviceDataTapeLNPDF(_DeviceDataTarget):
     every dimension it reaches.  A gradient call of ``DeviceDataLNPDF`` takes a sixth of the time at D = 32, under a half at
     D = 128 and the same time at D = 512, because its dual numbers stay in registers while a tape goes through memory; this
     class is for num_dimensions above ``_lib.CUSTOM_AUTODIFF_MAX_DIM``.
-    Neither class chooses for the other."""
+    Neither class chooses for the other.  eval_sets, report_waic: as for ``DeviceDataLNPDF``."""
 
     _mode = "data_tape"
 
-    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, tape_capacity=None, scratch_bytes=None):
+    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, tape_capacity=None, scratch_bytes=None,
+                 eval_sets=None, report_waic=False):
         for name, value in (("tape_capacity", tape_capacity), ("scratch_bytes", scratch_bytes)):
             if value is not None and (int(value) != value or int(value) < 1):
                 raise ValueError(f"{name} must be a positive integer or None, got {value!r}")
         self.tape_capacity = 0 if tape_capacity is None else int(tape_capacity)
         self.scratch_bytes = 0 if scratch_bytes is None else int(scratch_bytes)
-        super().__init__(source, num_dimensions, data, params, batch_size, seed)
+        super().__init__(source, num_dimensions, data, params, batch_size, seed, eval_sets, report_waic)
 
     def _check_dimension(self, num_dimensions):
         if num_dimensions > _lib.MAX_DIM_DIAG:

@@ -169,6 +169,31 @@ def custom_data_plan(n, rows, chunks_requested=0):
     return chunks.value, per.value
 
 
+def custom_data_predictive_plan(n, rows, chunks_requested=0):
+    """The launch plan of ``custom_data_predictive`` for n samples and an evaluation set of ``rows``
+    (gmmvi_custom_data_predictive_plan; needs no device) -> (tiles, chunks, rows_per_chunk)."""
+    import ctypes as C
+    tiles, chunks, per = C.c_int(), C.c_int(), C.c_int64()
+    lib = _lib.load()
+    _lib.check(None, lib.gmmvi_custom_data_predictive_plan(int(n), int(rows), int(chunks_requested), C.byref(tiles),
+                                                           C.byref(chunks), C.byref(per)))
+    return tiles.value, chunks.value, per.value
+
+
+def custom_data_predictive_probe(l, chunks_requested=0):
+    """The tile reduction and the tile merge of the predictive kernels on the host (gmmvi_custom_data_predictive_probe; needs no
+    device) for a host matrix l [n, rows] of row terms -> (lpd [rows], mean [rows], var [rows]) as NumPy arrays."""
+    l = np.ascontiguousarray(l, np.float32)
+    if l.ndim != 2:
+        raise ValueError(f"l: expected a two-dimensional array, got {l.shape}")
+    n, m = l.shape
+    out = [np.empty(m, np.float32) for _ in range(3)]
+    lib = _lib.load()
+    _lib.check(None, lib.gmmvi_custom_data_predictive_probe(l.ctypes.data, n, m, int(chunks_requested),
+                                                            *[o.ctypes.data for o in out]))
+    return tuple(out)
+
+
 class CustomTarget:
     """A compiled user target of a context (gmmvi_custom_target); released with the object."""
 
@@ -305,6 +330,33 @@ def target_custom_data_tape(ctx, handle, params, data, x, want_grad=True, batch_
             int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks), int(tape_capacity),
             int(scratch_bytes)))
     return lp, grad
+
+
+def custom_data_predictive(ctx, handle, params, rows, x, chunks=0):
+    """Predictive density of a handle of mode "data" or "data_tape" (csrc/custom_target_data.inc): with l[n, m] the row term of
+    sample x[n] on rows[m], per row  lpd = log mean_n exp(l),  mean = mean_n l  and  var = the unbiased variance of l over the
+    samples.  rows [M, C]: the evaluation set; chunks: 0 lets the library plan the launch, a positive number forces that many
+    row chunks (no output bit depends on it).  -> (lpd [M], mean [M], var [M])."""
+    if not isinstance(handle, CustomTarget):
+        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
+    if len(x.shape) != 2:
+        raise ValueError(f"x: expected a two-dimensional array, got {x.shape}")
+    n, d = x.shape
+    _req(x, (n, d), name="x")
+    if len(rows.shape) != 2:
+        raise ValueError(f"rows: expected a two-dimensional array, got {rows.shape}")
+    m, c = rows.shape
+    _req(rows, (m, c), name="rows")
+    if n < 1 or m < 1:
+        raise ValueError(f"the predictive density needs at least one sample and one row, got {n} and {m}")
+    if params is not None:
+        if len(params.shape) != 1:
+            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
+        _req(params, params.shape, name="params")
+    lpd, mean, var = ctx.empty((m,)), ctx.empty((m,)), ctx.empty((m,))
+    ctx.check(ctx.lib.gmmvi_custom_data_predictive(ctx.handle, handle.handle, d, None if params is None else params.ptr, rows.ptr, m,
+                                                   c, x.ptr, n, lpd.ptr, mean.ptr, var.ptr, int(chunks)))
+    return lpd, mean, var
 
 
 def custom_tape_length(ctx, handle, d):

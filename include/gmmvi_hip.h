@@ -545,6 +545,50 @@ int gmmvi_data_tape_probe(int D, const float* params, const float* data, int64_t
                           uint32_t call, const float* X, int N, int chunks, int rows_per_chunk, int capacity, float* lp,
                           float* grad, int* needed);
 
+/* ---- predictive density of a data-set target -------------------------------------------------------------------------------------
+ * What a fitted posterior of the shape above is judged by: for samples X[N, D] of the approximation and an evaluation set
+ * rows[M, C] (held-out rows, or the training rows for WAIC), with  l[n, m] = gmmvi_user_row<float>(x_n, D, rows[m], C, params)
+ * (the float instantiation of a value call; the prior takes no part), per row m
+ *
+ *     lpd[m]  = log sum_n exp(l[n, m]) - log N      the log posterior-predictive density, max-shifted
+ *     mean[m] = (1 / N) sum_n l[n, m]
+ *     var[m]  = M2 / (N - 1),  M2 = sum_n (l[n, m] - mean[m])^2;  0 for N = 1          (the unbiased variance: WAIC's penalty)
+ *
+ * Kernels (csrc/custom_target_data.inc, in the code object of every handle of gmmvi_custom_target_compile_data and
+ * gmmvi_custom_target_compile_data_tape): the geometry of the value call, grid ceil(N / 64) x chunks, 4 waves on the same 64
+ * samples, lane = sample, x staged in LDS up to GMMVI_CUSTOM_STAGED_MAX_DIM; a workgroup owns rows_per_chunk consecutive rows of
+ * the evaluation set, its wave w the positions w, w + 4, ... of them, the row wave-uniform.
+ * Reduction order, all fp32, no atomics: for its row the wave reduces over its 64 lanes with an xor butterfly (1, 2, 4, ..., 32):
+ * the maximum; with shift = the maximum if finite, else 0, the sum of exp(l - shift); the sum of l, divided by the tile's count
+ * (the tile mean); the sum of (l - tile mean)^2.  Lanes past N take no part: -inf to the maximum, 0 to the sums, and the count is
+ * the number of valid lanes.  One tile: lane 0 finishes the row in place.  More: lane 0 writes (max, sumexp, mean, M2) to the
+ * context's scratch, tiles * M * 4 floats, and a second kernel (thread = row) merges the tiles IN TILE-INDEX ORDER: the
+ * log-sum-exp pairs by rescaling both to the shift of the larger maximum, and with  delta = mean_t - mean, n' = n + c_t:
+ * mean += delta c_t / n',  M2 += M2_t + delta^2 n c_t / n'.  Then  lpd = (shift + log sumexp) - log N.
+ * The same inputs give the same bits, and so does every chunk request: chunks split the rows, never a reduction.
+ * Edge values of lpd: a column that is -inf at every sample gives -inf exactly (no -inf - (-inf): the shift is 0, and a partial
+ * whose sumexp is 0 is not rescaled); -inf at some samples gives the finite log-sum of the others; a +inf gives +inf; a NaN gives
+ * NaN (fmaxf drops it, the sum of exponentials carries it).  mean and var of a column that holds a non-finite value are whatever
+ * IEEE arithmetic gives; only lpd has guaranteed handling.
+ * The plan, a host function (no device, no context): *tiles = ceil(N / 64); *chunks and *rows_per_chunk by the rules of
+ * gmmvi_custom_data_plan over the M evaluation rows: auto (0) enough chunks that tiles * chunks reaches 256 but at most M / 32,
+ * at least 1; a request is honoured up to one row per chunk (and 65535); then rows_per_chunk = ceil(M / chunks), chunks =
+ * ceil(M / rows_per_chunk), the last chunk never empty.  N < 1, M outside 1 .. 2^31 - 1, a negative request or a NULL output:
+ * GMMVI_ERR_ARG. */
+int gmmvi_custom_data_predictive_plan(int N, int64_t M, int chunks_requested, int* tiles, int* chunks, int64_t* rows_per_chunk);
+/* lpd[M], and mean[M] / var[M] where the pointer is not NULL, of the handle's row term.  rows_dev[M, C] fp32, X_dev[N, D].
+ * GMMVI_ERR_ARG before any launch, with a message: a NULL handle, rows_dev, X_dev or lpd_out_dev; a handle of another context; a
+ * handle that was not compiled by gmmvi_custom_target_compile_data or gmmvi_custom_target_compile_data_tape (the message names
+ * them); N < 1; M outside 1 .. 2^31 - 1; C < 1; D outside 1 .. GMMVI_MAX_DIM_DIAG; chunks_requested < 0.  No synchronisation.
+ * Profiling tags: custom_data_predictive, custom_data_predictive_merge. */
+int gmmvi_custom_data_predictive(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                                 const float* rows_dev, int64_t M, int C, const float* X_dev, int N, float* lpd_out_dev,
+                                 float* mean_out_dev, float* var_out_dev, int chunks_requested);
+/* The tile reduction and the tile merge of those kernels on the host (no device, no context; csrc/predictive_probe.hip compiles
+ * the very functions of the device text behind a 64-wide vector as the lane type) on a host matrix l[N, M] of row terms, for the
+ * plan of (N, M, chunks_requested).  Writes lpd[M], mean[M], var[M]; a NULL array or a refused plan: GMMVI_ERR_ARG. */
+int gmmvi_custom_data_predictive_probe(const float* l, int N, int64_t M, int chunks_requested, float* lpd, float* mean, float* var);
+
 /* ---- sampling -------------------------------------------------------------------------------------------- */
 /* x = mu_k + L_k eps for offsets[k] <= n < offsets[k+1] (component order), mapping[n] = k.
  * Replaces GMM.sample_from_components_no_shuffle + FullCovGMM.sample_from_component
