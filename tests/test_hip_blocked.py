@@ -84,7 +84,8 @@ def test_blocked_mixture_eval_component_chunks(ctx, rng):
     packed, _ = ops().pack_components(ctx, means, chols)
     xd = ctx.asarray(x)
     ld, lp, grad = ops().mixture_eval(ctx, packed, logw, xd, d, want_ld=True, want_lp=True, want_grad=True)
-    os.environ["GMMVI_BLOCKED_ZBYTES"] = str(2 * n * d * 4)          # two components per chunk
+    lp_stride = (d + 1 + 3) // 4 * 4                                 # the budget is divided by the row stride of Z, not by D
+    os.environ["GMMVI_BLOCKED_ZBYTES"] = str(2 * n * lp_stride * 4)  # two components per chunk: 2 + 2 + 1
     try:
         ld2, lp2, grad2 = ops().mixture_eval(ctx, packed, logw, xd, d, want_ld=True, want_lp=True, want_grad=True)
         _, lp3, grad3 = ops().mixture_eval(ctx, packed, logw, xd, d, want_grad=True)
