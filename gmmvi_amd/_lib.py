@@ -195,6 +195,7 @@ _PROTOS = {
     "gmmvi_custom_target_compile_data": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i)]),
     "gmmvi_target_custom_data": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i]),
+    "gmmvi_target_custom_data_own_batches": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i]),
     "gmmvi_custom_target_check_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_tape_plan": (_i, [_i, _i, _sz, C.POINTER(_i), C.POINTER(_i)]),
@@ -205,6 +206,8 @@ _PROTOS = {
     "gmmvi_custom_target_compile_data_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
     "gmmvi_target_custom_data_tape": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i, _i, _sz]),
+    "gmmvi_target_custom_data_tape_own_batches": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, C.c_int64, _u64, _u32, _p, _i, _p, _p, _i, _i,
+                                                       _sz]),
     "gmmvi_data_tape_probe": (_i, [_i, _p, _p, C.c_int64, _i, _i, C.c_int64, _u64, _u32, _p, _i, _i, _i, _i, _p, _p, C.POINTER(_i)]),
     "gmmvi_custom_data_predictive_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_int64)]),
     "gmmvi_custom_data_predictive": (_i, [_p, _p, _i, _p, _p, C.c_int64, _i, _p, _i, _p, _p, _p, _i]),

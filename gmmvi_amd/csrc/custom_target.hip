@@ -7,8 +7,9 @@
 // Targets summed over a data set (gmmvi_custom_target_compile_data): the user's source defines gmmvi_user_row and
 // gmmvi_user_prior; behind it go the dual-number text without its adapter, the tile mover of the wrapper text, the Feistel
 // stream (feistel.h and philox.h, made one string by the Makefile) and the kernels of custom_target_data.inc, which
-// gmmvi_target_custom_data launches.  The same text ends with the predictive kernels (the reduction over the samples of the row
-// terms on an evaluation set), which gmmvi_custom_data_predictive launches for a handle of either data mode.
+// gmmvi_target_custom_data launches, and gmmvi_target_custom_data_own_batches their own-batch instances.  The same text ends
+// with the predictive kernels (the reduction over the samples of the row terms on an evaluation set), which
+// gmmvi_custom_data_predictive launches for a handle of either data mode.
 // Targets differentiated on a tape (gmmvi_custom_target_compile_tape): the source of the differentiated mode, unchanged; behind it
 // goes custom_target_tape.inc alone, the tape's number type and its two kernels, which gmmvi_target_custom_tape launches.
 // Targets summed over a data set and differentiated on a tape (gmmvi_custom_target_compile_data_tape): the source of the data
@@ -154,9 +155,10 @@ struct gmmvi_custom_target {
     Mode mode = MODE_HAND;
     int refs = 0;
     hipModule_t module = nullptr;
-    hipFunction_t fn[11] = {};             // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
+    hipFunction_t fn[16] = {};             // staged lp, staged lp + grad, direct lp, direct lp + grad; MODE_DATA: merge lp, lp + grad;
                                            // MODE_TAPE: lp, lp + grad; MODE_DATA_TAPE: the six of MODE_DATA, tape rows, tape finish;
-                                           // both data modes: fn[8 .. 10] predictive staged, direct, merge
+                                           // both data modes: fn[8 .. 10] predictive staged, direct, merge; fn[11 .. 14] own-batch
+                                           // rows in the order of fn[0 .. 3]; MODE_DATA_TAPE: fn[15] own-batch tape rows
     mutable std::vector<std::pair<int, int>> tape_lengths;   // the tape modes: (D, the longest tape a gradient launch at that D has needed)
 };
 
@@ -242,6 +244,11 @@ static int compile_target(gmmvi_ctx* ctx, const char* source, Mode mode, gmmvi_c
                                                     "gmmvi_data_predictive_merge"};
     for (int i = 0; e == hipSuccess && i < 3 && (mode == MODE_DATA || mode == MODE_DATA_TAPE); ++i)
         e = hipModuleGetFunction(&t->fn[8 + i], t->module, predictive_names[i]);
+    static const char* const own_names[5] = {"gmmvi_data_rows_own_staged_lp", "gmmvi_data_rows_own_staged_grad",
+                                             "gmmvi_data_rows_own_direct_lp", "gmmvi_data_rows_own_direct_grad",
+                                             "gmmvi_data_tape_rows_own"};
+    for (int i = 0; e == hipSuccess && i < (mode == MODE_DATA ? 4 : mode == MODE_DATA_TAPE ? 5 : 0); ++i)
+        e = hipModuleGetFunction(&t->fn[11 + i], t->module, own_names[i]);
     if (e != hipSuccess) {
         if (t->module) (void)hipModuleUnload(t->module);
         delete t;
@@ -370,6 +377,9 @@ struct RowList {                 // gmmvi_data::RowList of custom_target_data.in
 static_assert(sizeof(RowList) == 36, "RowList is a kernel argument: its layout is the device text's");
 }  // namespace
 
+// minibatch inside the library: the flag of gmmvi_target_custom_data (0, 1), or own batches, which only the _own_batches entries pass
+constexpr int GMMVI_DATA_OWN_BATCHES = 2;
+
 // the refusals the two data modes share, in the order and with the messages of gmmvi_target_custom_data
 static int check_data_arguments(gmmvi_ctx* ctx, int D, const float* data_dev, int64_t T, int C, int minibatch, int64_t B,
                                 const float* X_dev, int N, const float* lp_out_dev, int chunks_requested) {
@@ -385,11 +395,13 @@ static int check_data_arguments(gmmvi_ctx* ctx, int D, const float* data_dev, in
     return GMMVI_OK;
 }
 
-// the launches of the data mode's kernels (fn[0 .. 5] of a handle of either data mode), dual-number gradient or value alone
+// the launches of the data mode's kernels (fn[0 .. 5] of a handle of either data mode, fn[11 .. 14] in place of fn[0 .. 3] for own
+// batches), dual-number gradient or value alone
 static int launch_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev, const float* data_dev, int64_t T,
                        int C, int minibatch, int64_t B, uint64_t seed, uint32_t call, const float* X_dev, int N, float* lp_out_dev,
                        float* grad_out_dev, int chunks_requested) {
     const bool want_grad = grad_out_dev != nullptr;
+    const bool own = minibatch == GMMVI_DATA_OWN_BATCHES;
     const int64_t length = minibatch ? B : T;
     int chunks = 0, rows_per_chunk = 0;
     if (gmmvi_custom_data_plan(N, length, chunks_requested, &chunks, &rows_per_chunk) != GMMVI_OK)
@@ -414,9 +426,9 @@ static int launch_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, cons
                        sizeof(float);
     {
         void* args[] = {&D, &params_dev, &X_dev, &N, &data_dev, &l, &scale, &lp_out_dev, &grad_out_dev, &part_lp, &part_grad};
-        GMMVI_PROF(ctx, "target_custom_data");
-        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[(staged ? 0 : 2) + (want_grad ? 1 : 0)], (unsigned)tiles, (unsigned)chunks, 1,
-                                                   256, 1, 1, (unsigned)lds, ctx->stream, args, nullptr));
+        GMMVI_PROF(ctx, own ? "target_custom_data_own" : "target_custom_data");
+        GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[(own ? 11 : 0) + (staged ? 0 : 2) + (want_grad ? 1 : 0)], (unsigned)tiles,
+                                                   (unsigned)chunks, 1, 256, 1, 1, (unsigned)lds, ctx->stream, args, nullptr));
     }
     if (chunks > 1) {
         const size_t blocks = ((size_t)N + 255) / 256;
@@ -428,15 +440,17 @@ static int launch_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, cons
     return GMMVI_OK;
 }
 
-extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
-                                        const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
-                                        uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
-                                        int chunks_requested) {
+// gmmvi_target_custom_data (own == false) and gmmvi_target_custom_data_own_batches (own == true, minibatch == 1): one set of
+// refusals, one plan; own batches launch the kernels of their own
+static int target_custom_data(const char* entry, gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                              const float* data_dev, int64_t T, int C, int minibatch, bool own, int64_t B, uint64_t seed,
+                              uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                              int chunks_requested) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr);
     GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
     if (t->mode == MODE_DATA_TAPE) return refuse_data_tape(ctx);
     if (t->mode != MODE_DATA)
-        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_data needs a target compiled by "
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, std::string("invalid argument: ") + entry + " needs a target compiled by "
                                               "gmmvi_custom_target_compile_data; gmmvi_target_custom launches the other two kinds");
     const int rc = check_data_arguments(ctx, D, data_dev, T, C, minibatch, B, X_dev, N, lp_out_dev, chunks_requested);
     if (rc != GMMVI_OK) return rc;
@@ -444,8 +458,24 @@ extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_targe
         return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the gradient of a differentiated target needs D <= " +
                                                   std::to_string(GMMVI_CUSTOM_AUTODIFF_MAX_DIM) + ", got D = " + std::to_string(D) +
                                                   " (a value call runs above)");
-    return launch_data(ctx, t, D, params_dev, data_dev, T, C, minibatch, B, seed, call, X_dev, N, lp_out_dev, grad_out_dev,
-                       chunks_requested);
+    return launch_data(ctx, t, D, params_dev, data_dev, T, C, own ? GMMVI_DATA_OWN_BATCHES : minibatch, B, seed, call, X_dev, N,
+                       lp_out_dev, grad_out_dev, chunks_requested);
+}
+
+extern "C" int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                        const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
+                                        uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                        int chunks_requested) {
+    return target_custom_data("gmmvi_target_custom_data", ctx, t, D, params_dev, data_dev, T, C, minibatch, false, B, seed, call, X_dev,
+                              N, lp_out_dev, grad_out_dev, chunks_requested);
+}
+
+extern "C" int gmmvi_target_custom_data_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                                    const float* data_dev, int64_t T, int C, int64_t B, uint64_t seed, uint32_t call,
+                                                    const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                                    int chunks_requested) {
+    return target_custom_data("gmmvi_target_custom_data_own_batches", ctx, t, D, params_dev, data_dev, T, C, 1, true, B, seed, call,
+                              X_dev, N, lp_out_dev, grad_out_dev, chunks_requested);
 }
 
 // ---- predictive density of a data-set target: the reduction over the samples -------------------------------------------------------
@@ -671,19 +701,21 @@ extern "C" int gmmvi_custom_data_tape_plan(int N, int64_t rows, int D, int capac
     return GMMVI_OK;
 }
 
-extern "C" int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
-                                             const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
-                                             uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
-                                             int chunks_requested, int tape_capacity, size_t scratch_bytes) {
+// gmmvi_target_custom_data_tape (own == false) and gmmvi_target_custom_data_tape_own_batches (own == true, minibatch == 1)
+static int target_custom_data_tape(const char* entry, gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                   const float* data_dev, int64_t T, int C, int minibatch, bool own, int64_t B, uint64_t seed,
+                                   uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                   int chunks_requested, int tape_capacity, size_t scratch_bytes) {
     GMMVI_ARG_CHECK(ctx, ctx != nullptr);
     GMMVI_ARG_CHECK(ctx, t != nullptr && find_target(ctx, t) != ctx->custom_targets.end());
     if (t->mode != MODE_DATA_TAPE)
-        return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: gmmvi_target_custom_data_tape needs a target compiled by "
+        return gmmvi_fail(ctx, GMMVI_ERR_ARG, std::string("invalid argument: ") + entry + " needs a target compiled by "
                                               "gmmvi_custom_target_compile_data_tape; gmmvi_target_custom, gmmvi_target_custom_data "
                                               "and gmmvi_target_custom_tape launch the other kinds");
     const int rc = check_data_arguments(ctx, D, data_dev, T, C, minibatch, B, X_dev, N, lp_out_dev, chunks_requested);
     if (rc != GMMVI_OK) return rc;
     GMMVI_ARG_CHECK(ctx, tape_capacity >= 0);
+    if (own) minibatch = GMMVI_DATA_OWN_BATCHES;
     if (!grad_out_dev)                                               // the data mode's value call: its kernels, its plan, its bits
         return launch_data(ctx, t, D, params_dev, data_dev, T, C, minibatch, B, seed, call, X_dev, N, lp_out_dev, nullptr,
                            chunks_requested);
@@ -724,8 +756,8 @@ extern "C" int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_
             const unsigned here = (unsigned)(tiles - first_tile < tiles_per_slab ? tiles - first_tile : tiles_per_slab);
             {
                 void* args[] = {&D, &params_dev, &X_dev, &N, &data_dev, &l, &first_tile, &rec, &adj, &acc, &cap, &needed_dev};
-                GMMVI_PROF(ctx, "target_custom_data_tape");
-                GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[6], here, (unsigned)chunks, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
+                GMMVI_PROF(ctx, own ? "target_custom_data_tape_own" : "target_custom_data_tape");
+                GMMVI_HIP_CHECK(ctx, hipModuleLaunchKernel(t->fn[own ? 15 : 6], here, (unsigned)chunks, 1, 64, 1, 1, 0, ctx->stream, args, nullptr));
             }
             {
                 void* args[] = {&D, &params_dev, &X_dev, &N, &chunks, &scale, &first_tile, &rec, &adj, &acc, &cap, &needed_dev,
@@ -753,4 +785,21 @@ extern "C" int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_
     }
     return gmmvi_fail(ctx, GMMVI_ERR_ARG, "invalid argument: the tape of the target grew between two launches on the same samples and "
                                           "rows: gmmvi_user_row or gmmvi_user_prior is not a pure function of x, D, the row and params");
+}
+
+extern "C" int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D, const float* params_dev,
+                                             const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed,
+                                             uint32_t call, const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                             int chunks_requested, int tape_capacity, size_t scratch_bytes) {
+    return target_custom_data_tape("gmmvi_target_custom_data_tape", ctx, t, D, params_dev, data_dev, T, C, minibatch, false, B, seed,
+                                   call, X_dev, N, lp_out_dev, grad_out_dev, chunks_requested, tape_capacity, scratch_bytes);
+}
+
+extern "C" int gmmvi_target_custom_data_tape_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_target* t, int D,
+                                                         const float* params_dev, const float* data_dev, int64_t T, int C, int64_t B,
+                                                         uint64_t seed, uint32_t call, const float* X_dev, int N, float* lp_out_dev,
+                                                         float* grad_out_dev, int chunks_requested, int tape_capacity,
+                                                         size_t scratch_bytes) {
+    return target_custom_data_tape("gmmvi_target_custom_data_tape_own_batches", ctx, t, D, params_dev, data_dev, T, C, 1, true, B, seed,
+                                   call, X_dev, N, lp_out_dev, grad_out_dev, chunks_requested, tape_capacity, scratch_bytes);
 }

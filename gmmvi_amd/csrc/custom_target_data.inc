@@ -13,6 +13,12 @@ R"GMMVI_DATA(
 // walk per wave and row, and the row's floats come through uniform loads.
 // Summation order (fixed, no atomics): within a wave in position order; wave 0 adds waves 1, 2, 3 in that order (LDS); chunks
 // in index order (gmmvi_data_merge_*, or not at all with one chunk); then  s * sum,  then  + prior.
+// gmmvi_data_rows_own_*: the same geometry, launch plan and summation order for own batches (minibatch == 2): every sample draws
+// its own batch, so lane = sample reads its own row: position j of sample n is the stream position n B + j of (seed, call), with
+// n the sample's index in the call.  The lane computes the epoch and rank of its j = 0 once (own_origin: the one 64-bit division)
+// and walks the Feistel network itself for every position; the row pointer is a per-lane value, never made uniform, and the
+// row's floats come through per-lane vector loads.  A gradient call repeats the walk in each of its ceil(D / W) passes: no
+// index scratch, no extra launch (DESIGN.md 6 has the timing).
 // params, X and the data set are __restrict__ kernel arguments: nothing a kernel stores can change them, which is what lets the
 // compiler keep the uniform loads of a row on the scalar path although the passes of a gradient call store in between.
 // LDS: [3][1 or 1 + W][64] wave accumulators, then (staged) the x image [64][D | 1].
@@ -26,7 +32,7 @@ constexpr int W = gmmvi_ad::W;
 struct RowList {                // of the data set data[T, C]
     int C;
     unsigned T;
-    int minibatch;              // 0: position p is row p; 1: row pi(p) of the stream of (seed, call)
+    int minibatch;              // 0: position p is row p; 1: row pi(p) of the stream of (seed, call); 2: own batches (own_row_at)
     unsigned length;            // T, or the batch size
     unsigned rows_per_chunk;
     unsigned call, hbits, k0, k1;
@@ -37,6 +43,28 @@ __device__ __forceinline__ const float* row_at(const float* data, const RowList&
     if (l.minibatch) r = gmmvi_feistel_permute(p, 0u, l.call, GMMVI_STREAM_DATA_MINIBATCH, l.T, l.hbits, l.k0, l.k1);
     r = (unsigned)__builtin_amdgcn_readfirstlane((int)r);
     return data + (size_t)r * (size_t)l.C;
+}
+
+// Own batches: stream position n B + j has epoch (n B + j) div T and rank (n B + j) mod T.  The origin is the epoch and rank of
+// j = 0 of the lane's sample; j < B <= T, so rank + j wraps at most once.  n < 2^31 and B <= T keep the epoch below 2^31.
+struct OwnOrigin { unsigned epoch, rank; };
+
+__device__ __forceinline__ OwnOrigin own_origin(size_t n, const RowList& l) {
+    const unsigned long long base = (unsigned long long)n * l.length;
+    return {(unsigned)(base / l.T), (unsigned)(base % l.T)};
+}
+
+// the row of position j of the lane's batch: a per-lane pointer
+__device__ __forceinline__ const float* own_row_at(const float* data, const RowList& l, OwnOrigin o, unsigned j) {
+    unsigned r = o.rank + j, e = o.epoch;
+    if (r >= l.T) { r -= l.T; ++e; }
+    r = gmmvi_feistel_permute(r, e, l.call, GMMVI_STREAM_DATA_MINIBATCH, l.T, l.hbits, l.k0, l.k1);
+    return data + (size_t)r * (size_t)l.C;
+}
+
+template <bool OWN>
+__device__ __forceinline__ const float* row_of(const float* data, const RowList& l, OwnOrigin o, unsigned p) {
+    if constexpr (OWN) return own_row_at(data, l, o, p); else return row_at(data, l, p);
 }
 
 // wave 0 receives the sum of the four waves' `count` floats per lane, added in the order 0, 1, 2, 3; two barriers
@@ -67,7 +95,7 @@ __device__ __forceinline__ Dual finish_pass(const Dual& sum, float scale, const 
     return scaled + gmmvi_user_prior<Dual, Seed>(Seed{x, first}, D, params);
 }
 
-template <bool GRAD, bool STAGED>
+template <bool GRAD, bool STAGED, bool OWN>
 __device__ __forceinline__ void rows(int D, const float* params, const float* X, int N, const float* data, RowList l, float scale,
                                      float* lp, float* grad, float* part_lp, float* part_grad) {
     extern __shared__ float gmmvi_data_lds[];
@@ -97,11 +125,13 @@ __device__ __forceinline__ void rows(int D, const float* params, const float* X,
     const unsigned end = l.length - begin < l.rows_per_chunk ? l.length : begin + l.rows_per_chunk;
     const size_t n = n0 + lane;
     const size_t slot = (size_t)chunk * (size_t)N + n;    // of the partials
+    OwnOrigin o{};
+    if constexpr (OWN) o = own_origin(n0 + mine, l);      // the sample's index in the call; lanes past N walk the last sample's batch
 
     if constexpr (!GRAD) {
         float acc[1] = {0.f};
         for (unsigned p = begin + w; p < end; p += 4)
-            acc[0] += gmmvi_user_row<float, const float*>(x, D, row_at(data, l, p), l.C, params);
+            acc[0] += gmmvi_user_row<float, const float*>(x, D, row_of<OWN>(data, l, o, p), l.C, params);
         merge_waves<1>(acc, red, w, lane);
         if (w == 0) {
             if (single) {
@@ -115,7 +145,7 @@ __device__ __forceinline__ void rows(int D, const float* params, const float* X,
         for (int first = 0; first < D; first += W) {
             Dual sum(0.f);
             for (unsigned p = begin + w; p < end; p += 4)
-                sum += gmmvi_user_row<Dual, Seed>(Seed{x, first}, D, row_at(data, l, p), l.C, params);
+                sum += gmmvi_user_row<Dual, Seed>(Seed{x, first}, D, row_of<OWN>(data, l, o, p), l.C, params);
             float acc[COUNT];
             acc[0] = sum.v;
 #pragma unroll
@@ -176,18 +206,22 @@ __device__ __forceinline__ void merge(int D, const float* params, const float* X
 
 }  // namespace gmmvi_data
 
-#define GMMVI_DATA_ROWS_KERNEL(name, GRAD, STAGED)                                                                          \
+#define GMMVI_DATA_ROWS_KERNEL(name, GRAD, STAGED, OWN)                                                                        \
     extern "C" __global__ __launch_bounds__(256) void name(int D, const float* __restrict__ params,                         \
                                                            const float* __restrict__ X, int N,                             \
                                                            const float* __restrict__ data, gmmvi_data::RowList l,          \
                                                            float scale, float* lp, float* grad, float* part_lp,            \
                                                            float* part_grad) {                                             \
-        gmmvi_data::rows<GRAD, STAGED>(D, params, X, N, data, l, scale, lp, grad, part_lp, part_grad);                     \
+        gmmvi_data::rows<GRAD, STAGED, OWN>(D, params, X, N, data, l, scale, lp, grad, part_lp, part_grad);                \
     }
-GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_staged_lp, false, true)
-GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_staged_grad, true, true)
-GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_direct_lp, false, false)
-GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_direct_grad, true, false)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_staged_lp, false, true, false)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_staged_grad, true, true, false)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_direct_lp, false, false, false)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_direct_grad, true, false, false)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_own_staged_lp, false, true, true)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_own_staged_grad, true, true, true)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_own_direct_lp, false, false, true)
+GMMVI_DATA_ROWS_KERNEL(gmmvi_data_rows_own_direct_grad, true, false, true)
 #undef GMMVI_DATA_ROWS_KERNEL
 
 extern "C" __global__ __launch_bounds__(256) void gmmvi_data_merge_lp(int D, const float* __restrict__ params,

@@ -13,6 +13,8 @@ R"GMMVI_DATA_TAPE(
 // gmmvi_user_row<Var, Input> on the wave's tape, adds the value to its running sum and, if the count is within the capacity,
 // walks the records back from the output node with seed 1, adding the adjoints of the inputs into its column of the wave's
 // accumulator.  The same short tape serves every row.
+// gmmvi_data_tape_rows_own: the same kernel for own batches: every lane reads the rows of its own batch (gmmvi_data::own_row_at,
+// a per-lane pointer), so the record counts of one position differ from lane to lane by the row as well as by x.
 // What keeps the adjoints of the previous row out of the current one: gmmvi_tape::push zeroes the adjoint slot of every record
 // it writes, so each record the sweep reads carries an adjoint written since the current row began.  Records made after the output node are
 // never visited: the sweep starts at the output's own record.
@@ -106,12 +108,14 @@ GMMVI_DATA_TAPE_FN int finish_lane(const float* x, int D, const float* params, i
 }  // namespace gmmvi_data_tape
 
 #ifndef GMMVI_DATA_TAPE_NO_KERNELS
-extern "C" __global__ __launch_bounds__(64) void gmmvi_data_tape_rows(int D, const float* __restrict__ params,
-                                                                       const float* __restrict__ X, int N,
-                                                                       const float* __restrict__ data, gmmvi_data::RowList l,
-                                                                       int first_tile, void* rec, float* adj, float* acc, int cap,
-                                                                       int* needed) {
-    using namespace gmmvi_data_tape;
+namespace gmmvi_data_tape {
+
+// the body of gmmvi_data_tape_rows (OWN = false) and of gmmvi_data_tape_rows_own (OWN = true: the lane's own batch, its rows
+// gmmvi_data::own_row_at from the origin of n, the sample's index in the call, whatever slab the launch serves)
+template <bool OWN>
+__device__ __forceinline__ void rows_kernel(int D, const float* params, const float* X, int N, const float* data,
+                                            const gmmvi_data::RowList& l, int first_tile, void* rec, float* adj, float* acc, int cap,
+                                            int* needed) {
     const int lane = (int)threadIdx.x;
     const size_t w = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
     const size_t tape_at = w * 64 * (size_t)cap;
@@ -126,11 +130,28 @@ extern "C" __global__ __launch_bounds__(64) void gmmvi_data_tape_rows(int D, con
     if (n >= (size_t)N) return;                                      // the lane's scratch columns stay unread
     const unsigned begin = blockIdx.y * l.rows_per_chunk;
     const unsigned end = l.length - begin < l.rows_per_chunk ? l.length : begin + l.rows_per_chunk;
-    const int longest = rows_lane(X + n * (size_t)D, D, params, l.C, [&](unsigned p) { return gmmvi_data::row_at(data, l, p); },
-                                  begin, end, (RecPtr)rec + tape_at + lane, (AdjPtr)adj + tape_at + lane, 64, cap,
+    gmmvi_data::OwnOrigin o{};
+    if constexpr (OWN) o = gmmvi_data::own_origin(n, l);
+    const int longest = rows_lane(X + n * (size_t)D, D, params, l.C,
+                                  [&](unsigned p) { return gmmvi_data::row_of<OWN>(data, l, o, p); }, begin, end,
+                                  (RecPtr)rec + tape_at + lane, (AdjPtr)adj + tape_at + lane, 64, cap,
                                   acc + w * 64 * (size_t)D + lane);
     atomicMax(needed, longest);
 }
+
+}  // namespace gmmvi_data_tape
+
+#define GMMVI_DATA_TAPE_ROWS_KERNEL(name, OWN)                                                                              \
+    extern "C" __global__ __launch_bounds__(64) void name(int D, const float* __restrict__ params,                          \
+                                                          const float* __restrict__ X, int N,                              \
+                                                          const float* __restrict__ data, gmmvi_data::RowList l,           \
+                                                          int first_tile, void* rec, float* adj, float* acc, int cap,      \
+                                                          int* needed) {                                                   \
+        gmmvi_data_tape::rows_kernel<OWN>(D, params, X, N, data, l, first_tile, rec, adj, acc, cap, needed);               \
+    }
+GMMVI_DATA_TAPE_ROWS_KERNEL(gmmvi_data_tape_rows, false)
+GMMVI_DATA_TAPE_ROWS_KERNEL(gmmvi_data_tape_rows_own, true)
+#undef GMMVI_DATA_TAPE_ROWS_KERNEL
 
 extern "C" __global__ __launch_bounds__(64) void gmmvi_data_tape_finish(int D, const float* __restrict__ params,
                                                                          const float* __restrict__ X, int N, int chunks,

@@ -8,7 +8,7 @@
 
 constexpr uint32_t GMMVI_STREAM_BNN_MINIBATCH = 3;       // bnn.hip, bnn_classifier.hip, bnn_mlp.hip
 constexpr uint32_t GMMVI_STREAM_LOGREG_MINIBATCH = 4;    // logreg_mb.hip: epoch word 0, its own position rule
-constexpr uint32_t GMMVI_STREAM_DATA_MINIBATCH = 5;      // custom_target_data.inc: epoch word 0, batch row j is pi(j)
+constexpr uint32_t GMMVI_STREAM_DATA_MINIBATCH = 5;      // custom_target_data.inc: epoch word 0, batch row j is pi(j); own batches: the BNN layout
 
 // h for a permutation of [0, T)
 __host__ __device__ inline uint32_t gmmvi_feistel_half_bits(uint32_t T) {

@@ -182,8 +182,11 @@ class _DeviceDataTarget(MinibatchLNPDF):
                              f"{rows.shape}")
         return rows
 
-    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, eval_sets=None, report_waic=False):
+    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, use_own_batch_per_sample=False,
+                 eval_sets=None, report_waic=False):
         super().__init__(seed)
+        if use_own_batch_per_sample and batch_size is None:
+            raise ValueError("use_own_batch_per_sample needs a batch_size: without one every sample sees all rows")
         if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
             raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
         self._check_dimension(int(num_dimensions))
@@ -206,6 +209,7 @@ class _DeviceDataTarget(MinibatchLNPDF):
         self._data_columns = int(data.shape[1])
         self._eval_sets_dev = {} if eval_sets is None else {name: self.ctx.asarray(rows) for name, rows in eval_sets.items()}
         self.batch_size = None if batch_size is None else int(batch_size)
+        self.use_own_batch_per_sample = bool(use_own_batch_per_sample)
         self.num_data = int(data.shape[0])
         self._num_dimensions = int(num_dimensions)
         self._data_dev = self.ctx.asarray(data)
@@ -220,6 +224,10 @@ class _DeviceDataTarget(MinibatchLNPDF):
         if len(x.shape) != 2 or x.shape[1] != self._num_dimensions:
             raise ValueError(f"samples: expected [n, {self._num_dimensions}], got {x.shape}")
         return x
+
+    def _batch_keywords(self, batch_size):
+        """What a subclass adds to its ``hip_ops`` call for the row list: nothing for a shared batch or the full data."""
+        return {"own_batches": True} if self.use_own_batch_per_sample and batch_size is not None else {}
 
     def _launch(self, x, call, want_grad):
         return self._target_call(self._x(x), want_grad, self.batch_size, call)
@@ -269,8 +277,8 @@ class _DeviceDataTarget(MinibatchLNPDF):
 
 
 class DeviceDataLNPDF(_DeviceDataTarget):
-    """``DeviceDataLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0, eval_sets=None,
-    report_waic=False)``: ``source`` defines
+    """``DeviceDataLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0, use_own_batch_per_sample=False,
+    eval_sets=None, report_waic=False)``: ``source`` defines
     ``gmmvi_user_row`` and ``gmmvi_user_prior`` (contract: include/gmmvi_hip.h), ``data`` is the 2-D data set, uploaded once as
     fp32, and the target is ``prior(x) + s * sum_r row(x, data[r])``.
 
@@ -278,6 +286,10 @@ class DeviceDataLNPDF(_DeviceDataTarget):
     ``minibatch_stream.data_minibatch_rows(seed, call_count, B, T)``, one batch shared by all samples, with s = T / B, and
     ``call_count`` advances after each evaluation that receives at least one sample (the protocol of ``MinibatchLNPDF``);
     ``log_density_full(x)`` is then the full-data value in index order, counter untouched.
+    use_own_batch_per_sample=True (upstream's option of that name; it needs a batch size): sample n of an evaluation draws its
+    own B rows, row n of ``minibatch_stream.data_minibatch_rows_per_sample(seed, call_count, N, B, T)``, so the minibatch error
+    differs from sample to sample instead of shifting a whole iteration; sample 0 sees the shared batch of the same call.  The
+    counter, ``log_density_full``, ``log_predictive`` and ``waic`` are as without it.
     The gradient comes from the library's dual numbers (num_dimensions <= _lib.CUSTOM_AUTODIFF_MAX_DIM) and is computed only
     for an estimator that reads it.  There is no ``_fast_path_target``: the iteration runs module by module, as for the other
     minibatch targets.
@@ -295,12 +307,13 @@ class DeviceDataLNPDF(_DeviceDataTarget):
 
     def _target_call(self, x, want_grad, batch_size, call):
         return hip_ops.target_custom_data(self.ctx, self._handle, self._params_dev, self._data_dev, x, want_grad=want_grad,
-                                          batch_size=batch_size, seed=self.seed, call=call)
+                                          batch_size=batch_size, seed=self.seed, call=call, **self._batch_keywords(batch_size))
 
 
 class DeviceDataTapeLNPDF(_DeviceDataTarget):
-    """``DeviceDataTapeLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0, tape_capacity=None,
-    scratch_bytes=None, eval_sets=None, report_waic=False)``: the source, the data, the minibatches, the call counter and the values of a ``DeviceDataLNPDF``, with
+    """``DeviceDataTapeLNPDF(source, num_dimensions, data, params=None, batch_size=None, seed=0, use_own_batch_per_sample=False,
+    tape_capacity=None, scratch_bytes=None, eval_sets=None, report_waic=False)``: the source, the data, the minibatches (shared or
+    one per sample), the call counter and the values of a ``DeviceDataLNPDF``, with
     the gradient from reverse mode (csrc/custom_target_data_tape.inc): every sample records one row's term at a time on a short
     tape in device scratch, reused for every row, and walks it back into a gradient accumulator.  The cost per row does not grow
     with ``ceil(D / 16)``, and ``num_dimensions`` goes up to ``_lib.MAX_DIM_DIAG``.
@@ -313,18 +326,21 @@ class DeviceDataTapeLNPDF(_DeviceDataTarget):
     every dimension it reaches.  A gradient call of ``DeviceDataLNPDF`` takes a sixth of the time at D = 32, under a half at
     D = 128 and the same time at D = 512, because its dual numbers stay in registers while a tape goes through memory; this
     class is for num_dimensions above ``_lib.CUSTOM_AUTODIFF_MAX_DIM``.
+    use_own_batch_per_sample: as for ``DeviceDataLNPDF``.  Own batches cost this class 5 - 8 % of a gradient call and the forward
+    route 11 % at D = 32, 89 % at D = 128 and 2.1 x at D = 512 (per-lane row loads in every pass), so toward the forward cap this
+    class is the faster own-batch route as well.
     Neither class chooses for the other.  eval_sets, report_waic: as for ``DeviceDataLNPDF``."""
 
     _mode = "data_tape"
 
-    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, tape_capacity=None, scratch_bytes=None,
-                 eval_sets=None, report_waic=False):
+    def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, use_own_batch_per_sample=False,
+                 tape_capacity=None, scratch_bytes=None, eval_sets=None, report_waic=False):
         for name, value in (("tape_capacity", tape_capacity), ("scratch_bytes", scratch_bytes)):
             if value is not None and (int(value) != value or int(value) < 1):
                 raise ValueError(f"{name} must be a positive integer or None, got {value!r}")
         self.tape_capacity = 0 if tape_capacity is None else int(tape_capacity)
         self.scratch_bytes = 0 if scratch_bytes is None else int(scratch_bytes)
-        super().__init__(source, num_dimensions, data, params, batch_size, seed, eval_sets, report_waic)
+        super().__init__(source, num_dimensions, data, params, batch_size, seed, use_own_batch_per_sample, eval_sets, report_waic)
 
     def _check_dimension(self, num_dimensions):
         if num_dimensions > _lib.MAX_DIM_DIAG:
@@ -335,4 +351,5 @@ class DeviceDataTapeLNPDF(_DeviceDataTarget):
         first = want_grad and self.tape_capacity and hip_ops.custom_tape_length(self.ctx, self._handle, self._num_dimensions) == 0
         return hip_ops.target_custom_data_tape(self.ctx, self._handle, self._params_dev, self._data_dev, x, want_grad=want_grad,
                                                batch_size=batch_size, seed=self.seed, call=call,
-                                               tape_capacity=self.tape_capacity if first else 0, scratch_bytes=self.scratch_bytes)
+                                               tape_capacity=self.tape_capacity if first else 0, scratch_bytes=self.scratch_bytes,
+                                               **self._batch_keywords(batch_size))

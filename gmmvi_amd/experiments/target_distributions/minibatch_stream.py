@@ -6,7 +6,8 @@ A stream permutes the T training rows by pi_{seed,call,epoch}, a balanced 4-roun
 of Philox4x32-10 with key (seed lo, seed hi) and counter (R | i << 24, epoch, call, stream).  Stream ids 0-2 are the
 samplers (component normals, categorical draws, mixture normals); 3 is the Bayesian neural networks' stream
 (``minibatch_rows`` below), 4 the minibatch logistic regressions' (epoch word 0, ``logistic_regression.minibatch_rows``), 5
-the minibatches of user-defined targets summed over a data set (epoch word 0, ``data_minibatch_rows`` below).
+the minibatches of user-defined targets summed over a data set (``data_minibatch_rows`` below: epoch word 0, one batch per
+call; ``data_minibatch_rows_per_sample``: the BNN stream's layout, a batch per sample).
 """
 import numpy as np
 
@@ -74,6 +75,19 @@ def data_minibatch_rows(seed, call, batch_size, num_data):
         raise ValueError(f"batch_size must be in 1..{num_data}, got {batch_size}")
     j = np.arange(int(batch_size), dtype=np.int64)
     return permute_rows(seed, call, np.zeros_like(j), j, num_data, stream=STREAM_DATA_MINIBATCH)
+
+
+def data_minibatch_rows_per_sample(seed, call, n, batch_size, num_data):
+    """The data rows of the n minibatches of call ``call`` of a ``DeviceDataLNPDF(use_own_batch_per_sample=True)``: int64
+    [n, batch_size].  Row j of sample i has stream position p = i * batch_size + j, epoch p div T and rank p mod T on stream 5
+    (the layout of ``minibatch_rows``).  Row 0 is ``data_minibatch_rows`` of the same call; the batches of one epoch are
+    disjoint; a batch that straddles an epoch boundary takes its tail from the next epoch and may hold one row twice;
+    batch_size == num_data gives every sample a permutation of all rows."""
+    if not 1 <= int(batch_size) <= int(num_data):
+        raise ValueError(f"batch_size must be in 1..{num_data}, got {batch_size}")
+    p = np.arange(int(n) * int(batch_size), dtype=np.int64)
+    rows = permute_rows(seed, call, p // num_data, p % num_data, num_data, stream=STREAM_DATA_MINIBATCH)
+    return rows.reshape(int(n), int(batch_size))
 
 
 class MinibatchLNPDF(LNPDF):

@@ -254,11 +254,14 @@ def target_custom(ctx, handle, params, x, want_grad=True, route=0):
     return lp, grad
 
 
-def target_custom_data(ctx, handle, params, data, x, want_grad=True, batch_size=None, seed=0, call=0, chunks=0):
+def target_custom_data(ctx, handle, params, data, x, want_grad=True, batch_size=None, seed=0, call=0, chunks=0, own_batches=False):
     """Data-mode user target ``handle`` on x [n, D]: prior(x) + s * sum of the row terms over data [T, C]
     (csrc/custom_target_data.inc).  batch_size None: all rows in index order, s = 1; a number: the minibatch of (seed, call)
-    with s = T / batch_size.  chunks: 0 lets the library plan the launch, a positive number forces that many row chunks.
-    -> (lp [n], grad [n, D] or None)."""
+    with s = T / batch_size, one batch shared by all samples or, with own_batches, a batch of its own for every sample
+    (``minibatch_stream.data_minibatch_rows_per_sample``; gmmvi_target_custom_data_own_batches).  chunks: 0 lets the library plan
+    the launch, a positive number forces that many row chunks.  -> (lp [n], grad [n, D] or None)."""
+    if own_batches and batch_size is None:
+        raise ValueError("own_batches needs a batch_size: the full-data row list is the same for every sample")
     if not isinstance(handle, CustomTarget):
         raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
     n, d = x.shape
@@ -273,7 +276,11 @@ def target_custom_data(ctx, handle, params, data, x, want_grad=True, batch_size=
         _req(params, params.shape, name="params")
     lp = ctx.empty((n,))
     grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0:
+    if n > 0 and own_batches:
+        ctx.check(ctx.lib.gmmvi_target_custom_data_own_batches(
+            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c, int(batch_size),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks)))
+    elif n > 0:
         ctx.check(ctx.lib.gmmvi_target_custom_data(
             ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c,
             0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
@@ -304,11 +311,14 @@ def target_custom_tape(ctx, handle, params, x, want_grad=True, tape_capacity=0, 
 
 
 def target_custom_data_tape(ctx, handle, params, data, x, want_grad=True, batch_size=None, seed=0, call=0, chunks=0,
-                            tape_capacity=0, scratch_bytes=0):
+                            tape_capacity=0, scratch_bytes=0, own_batches=False):
     """``target_custom_data`` for a handle of mode "data_tape": the same target, the same value call, and the gradient from
     reverse mode on a tape that is reused for every row (csrc/custom_target_data_tape.inc), at any D up to ``_lib.MAX_DIM_DIAG``.
     tape_capacity: records per lane, 0 what the handle has needed at this D so far; scratch_bytes: the budget of the tapes and
-    accumulators, 0 the default.  A gradient call synchronises the stream.  -> (lp [n], grad [n, D] or None)."""
+    accumulators, 0 the default.  own_batches: as for ``target_custom_data`` (gmmvi_target_custom_data_tape_own_batches).  A
+    gradient call synchronises the stream.  -> (lp [n], grad [n, D] or None)."""
+    if own_batches and batch_size is None:
+        raise ValueError("own_batches needs a batch_size: the full-data row list is the same for every sample")
     if not isinstance(handle, CustomTarget):
         raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
     n, d = x.shape
@@ -323,7 +333,12 @@ def target_custom_data_tape(ctx, handle, params, data, x, want_grad=True, batch_
         _req(params, params.shape, name="params")
     lp = ctx.empty((n,))
     grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0:
+    if n > 0 and own_batches:
+        ctx.check(ctx.lib.gmmvi_target_custom_data_tape_own_batches(
+            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c, int(batch_size),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks),
+            int(tape_capacity), int(scratch_bytes)))
+    elif n > 0:
         ctx.check(ctx.lib.gmmvi_target_custom_data_tape(
             ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c,
             0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,

@@ -424,6 +424,32 @@ int gmmvi_custom_data_plan(int N, int64_t rows, int chunks_requested, int* chunk
 int gmmvi_target_custom_data(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
                              const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed, uint32_t call,
                              const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int chunks_requested);
+/* Own minibatch per sample (upstream's use_own_batch_per_sample=True): the target above with a row list R_n of its own for every
+ * sample n, n the sample's index IN THE CALL (never inside a tile, slab or launch).  For (seed, call), batch size B and T rows,
+ * row j of sample n has the 64-bit stream position p = n B + j, epoch e = p div T and rank r = p mod T, and is data row
+ *
+ *     pi(r) = gmmvi_feistel_permute(r, e, call, stream 5, T, h, seed lo, seed hi)
+ *
+ * (csrc/feistel.h; the layout of the BNN stream, gmmvi_bnn_stream_origin_of / _row, on the data targets' stream id; NumPy:
+ * minibatch_stream.data_minibatch_rows_per_sample).  R_n = { row j : 0 <= j < B } in the order of j, s = (float)T / (float)B.
+ *   - sample 0's batch is exactly the shared batch of gmmvi_target_custom_data for the same (seed, call);
+ *   - an epoch is one permutation of all rows, so within an epoch the batches of different samples are disjoint;
+ *   - a batch that straddles an epoch boundary takes its tail from the next epoch's permutation and may hold one row twice;
+ *   - B == T gives every sample its own permutation of all rows (sample n the whole of epoch n), with s = 1.
+ * Range: N B may exceed 2^32 (p is formed in 64 bits); the epoch is at most (N B - 1) div T < N < 2^31 because B <= T,
+ * which the entry checks like its sibling, so nothing wraps.
+ * Kernels (csrc/custom_target_data.inc, gmmvi_data_rows_own_*): the geometry, the staged and direct x routes, the launch plan
+ * (gmmvi_custom_data_plan with rows = B) and the order of the arithmetic of gmmvi_target_custom_data, unchanged: a wave adds its
+ * positions j in order, wave 0 adds waves 1, 2, 3, chunks are added in index order, then s * sum, then + prior.  What differs:
+ * the row is a per-lane value, so every lane walks the Feistel network for its own (sample, position) and reads its row through
+ * vector loads; a gradient call repeats the walk in each of its ceil(D / W) passes (no index scratch).  The kernels and the bits
+ * of gmmvi_target_custom_data are untouched.
+ * Arguments of gmmvi_target_custom_data without the minibatch flag; the same refusals (B outside 1 .. T, T, C, N, D, the cap on D
+ * for a gradient, NULL pointers, a handle of another mode or context), each before any launch, outputs untouched.  Profiling
+ * tags: target_custom_data_own, target_custom_data_merge. */
+int gmmvi_target_custom_data_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                                         const float* data_dev, int64_t T, int C, int64_t B, uint64_t seed, uint32_t call,
+                                         const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int chunks_requested);
 
 /* ---- differentiated user-defined targets on a tape: reverse mode ------------------------------------------------------------------
  * The forward mode above costs ceil(D / W) passes and stops at GMMVI_CUSTOM_AUTODIFF_MAX_DIM.  This mode takes the same source,
@@ -536,6 +562,18 @@ int gmmvi_target_custom_data_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* tar
                                   const float* data_dev, int64_t T, int C, int minibatch, int64_t B, uint64_t seed, uint32_t call,
                                   const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev, int chunks_requested,
                                   int tape_capacity, size_t scratch_bytes);
+/* gmmvi_target_custom_data_tape with an own minibatch per sample: the row lists R_n of gmmvi_target_custom_data_own_batches, the
+ * arguments of gmmvi_target_custom_data_tape without the minibatch flag, its refusals, capacity and scratch rules.  A value call
+ * is the value call of gmmvi_target_custom_data_own_batches, kernel for kernel and bit for bit.  A gradient call launches
+ * gmmvi_data_tape_rows_own (csrc/custom_target_data_tape.inc: gmmvi_data_tape_rows with the lane's own row pointer; a slabbed
+ * launch forms the stream position from the sample's index in the call) and the unchanged finish kernel; the plan is
+ * gmmvi_custom_data_tape_plan with rows = B.  The readback of the tape length and the second attempt at the needed capacity use
+ * the same (seed, call), hence the same rows.  Profiling tags: target_custom_data_tape_own, target_custom_data_tape_finish
+ * (gradient call); target_custom_data_own, target_custom_data_merge (value call). */
+int gmmvi_target_custom_data_tape_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D, const float* params_dev,
+                                              const float* data_dev, int64_t T, int C, int64_t B, uint64_t seed, uint32_t call,
+                                              const float* X_dev, int N, float* lp_out_dev, float* grad_out_dev,
+                                              int chunks_requested, int tape_capacity, size_t scratch_bytes);
 /* The two lane bodies of csrc/custom_target_data_tape.inc on the host (no device, no context), lane stride 1, behind the
  * logistic-regression row term and prior of csrc/custom_data_tape_sample.hip (row = [features (D) | label], params = [prior mean,
  * prior std]): all arrays are host arrays, the row list is that of gmmvi_target_custom_data for (minibatch, B, seed, call), the
