@@ -191,6 +191,7 @@ _PROTOS = {
     "gmmvi_custom_target_check_autodiff": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_autodiff": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_autodiff_probe": (_i, [_i, _f, _f, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
+    "gmmvi_autodiff_probe_special": (_i, [_i, _f, _f, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
     "gmmvi_custom_target_check_data": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i)]),
@@ -202,6 +203,7 @@ _PROTOS = {
     "gmmvi_custom_tape_length": (_i, [_p, _p, _i, C.POINTER(_i)]),
     "gmmvi_target_custom_tape": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _sz]),
     "gmmvi_tape_probe": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "gmmvi_tape_probe_special": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gmmvi_custom_target_check_data_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -276,6 +278,14 @@ def _autodiff_ops():
 
 
 AUTODIFF_OPS = _autodiff_ops()
+
+# The operations of gmmvi_autodiff_probe_special and gmmvi_tape_probe_special in index order (csrc/autodiff_probe.hip): the special
+# functions of user-defined targets.  A trailing ``f``: the f-suffixed spelling (lgamma has none on a number: lgammaf stays
+# ROCm's float function); the library's own functions go by their names
+# without ``gmmvi_``; ``_tf`` / ``_ft``: the second / the first operand is a float; ``trigamma`` is a float function only (a
+# constant: no tangent, no record).
+SPECIAL_OPS = ("lgamma", "erf", "erff", "erfc", "erfcf", "digamma", "sigmoid", "softplus", "log_sigmoid",
+               "logaddexp", "logaddexp_tf", "logaddexp_ft", "trigamma")
 
 
 def load():

@@ -1,9 +1,11 @@
 // gmmvi_autodiff_probe (include/gmmvi_hip.h): one operation of the dual-number text of differentiated user-defined targets,
-// evaluated on the host.  The text is the one the run-time compiler gets (custom_target_autodiff.inc, its raw-string
-// delimiters taken off by the Makefile), without the adapter, which needs a user's function.  Host code only.
+// evaluated on the host; gmmvi_autodiff_probe_special: the same for its special functions, a list of their own.  The text is
+// the one the run-time compiler gets (custom_target_special.inc and custom_target_autodiff.inc, their raw-string delimiters
+// taken off by the Makefile), without the adapter, which needs a user's function.  Host code only.
 #include "common.h"
 
 #define GMMVI_AD_NO_ADAPTER
+#include "build/custom_target_special_text.inc"
 #include "build/custom_target_autodiff_text.inc"
 
 namespace {
@@ -51,6 +53,33 @@ extern "C" int gmmvi_autodiff_probe(int op, float a, float da, float b, float db
         case __COUNTER__ - kBase: r = Dual(gmmvi_value(A)); break;
         default:
             return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe: unknown operation " + std::to_string(op));
+    }
+    *value = r.v;
+    *tangent = r.d[0];
+    return GMMVI_OK;
+}
+
+// the special functions (custom_target_special.inc and their rules in the dual-number text), in the order of _lib.SPECIAL_OPS
+extern "C" int gmmvi_autodiff_probe_special(int op, float a, float da, float b, float db, float* value, float* tangent) {
+    if (!value || !tangent)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_special: value and tangent must not be NULL");
+    constexpr int kBase = __COUNTER__ + 1;
+    Dual A(a), B(b), r;
+    A.d[0] = da;
+    B.d[0] = db;
+    switch (op) {
+        case __COUNTER__ - kBase: r = lgamma(A); break;                    // lgammaf stays a float function
+        PROBE_UNARY(erf) PROBE_UNARY(erfc)
+        case __COUNTER__ - kBase: r = gmmvi_digamma(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_sigmoid(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_softplus(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_log_sigmoid(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_logaddexp(A, B); break;
+        case __COUNTER__ - kBase: r = gmmvi_logaddexp(A, b); break;
+        case __COUNTER__ - kBase: r = gmmvi_logaddexp(a, B); break;
+        case __COUNTER__ - kBase: r = Dual(gmmvi_trigamma(a)); break;      // a float function only: a constant
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_special: unknown operation " + std::to_string(op));
     }
     *value = r.v;
     *tangent = r.d[0];

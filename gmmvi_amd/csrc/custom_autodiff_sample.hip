@@ -16,5 +16,6 @@ __device__ T gmmvi_user_density(X x, int D, const float* params) {
     return lp;
 }
 
+#include "build/custom_target_special_text.inc"
 #include "build/custom_target_autodiff_text.inc"
 #include "build/custom_target_wrap_text.inc"

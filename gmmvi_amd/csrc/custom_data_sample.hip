@@ -30,6 +30,7 @@ __device__ T gmmvi_user_prior(X x, int D, const float* params) {
 
 #define GMMVI_AD_NO_ADAPTER
 #define GMMVI_WRAP_TILE_ONLY
+#include "build/custom_target_special_text.inc"
 #include "build/custom_target_autodiff_text.inc"
 #include "build/custom_target_wrap_text.inc"
 #include "feistel.h"

@@ -31,6 +31,7 @@ __host__ __device__ T gmmvi_user_prior(X x, int D, const float* params) {
 }
 
 #define GMMVI_TAPE_NO_KERNELS
+#include "build/custom_target_special_text.inc"
 #ifndef GMMVI_DATA_TAPE_PROBE
 #define GMMVI_AD_NO_ADAPTER
 #define GMMVI_WRAP_TILE_ONLY

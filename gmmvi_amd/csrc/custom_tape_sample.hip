@@ -18,4 +18,5 @@ __device__ T gmmvi_user_density(X x, int D, const float* params) {
     return lp;
 }
 
+#include "build/custom_target_special_text.inc"
 #include "build/custom_target_tape_text.inc"

@@ -2,6 +2,7 @@
 // gmmvi_user_target, this file appends the wrapper kernels of custom_target_wrap.inc, compiles both with hiprtc for the device
 // of the context, loads the code object and launches the wrapper on the context's stream.  hiprtc is bound with dlopen on
 // first use: the library links without it, and only a call that needs the compiler can miss it.
+// In every mode the float special functions of custom_target_special.inc go directly behind the user's source.
 // Differentiated targets (gmmvi_custom_target_compile_autodiff): the user's source defines gmmvi_user_density instead, and the
 // dual-number text of custom_target_autodiff.inc, which defines gmmvi_user_target on top of it, goes between the two.
 // Targets summed over a data set (gmmvi_custom_target_compile_data): the user's source defines gmmvi_user_row and
@@ -23,6 +24,9 @@
 static const char* const kWrapText =
 #include "custom_target_wrap.inc"
     ;
+static const char* const kSpecialText =
+#include "custom_target_special.inc"
+    ;
 static const char* const kAutodiffText =
 #include "custom_target_autodiff.inc"
     ;
@@ -38,8 +42,13 @@ static const char* const kDataTapeText =
 #include "custom_target_data_tape.inc"
     ;
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
-// the float instantiation of the user's template finds gmmvi_value only if it is declared before the template.
-static const char* const kAutodiffPrelude = "__host__ __device__ inline float gmmvi_value(float); ";
+// the float instantiation of the user's template finds gmmvi_value and the six functions of custom_target_special.inc only if
+// they are declared before the template.  The hand-written mode gets the same line: its float code calls the six too.
+static const char* const kAutodiffPrelude =
+    "__host__ __device__ inline float gmmvi_value(float); __host__ __device__ inline float gmmvi_digamma(float); "
+    "__host__ __device__ inline float gmmvi_trigamma(float); __host__ __device__ inline float gmmvi_sigmoid(float); "
+    "__host__ __device__ inline float gmmvi_softplus(float); __host__ __device__ inline float gmmvi_log_sigmoid(float); "
+    "__host__ __device__ inline float gmmvi_logaddexp(float, float); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
 
@@ -96,7 +105,9 @@ const Hiprtc& hiprtc() {
 int compile_source(const char* source, Mode mode, const char* arch, std::vector<char>& code, std::string& log) {
     const Hiprtc& rt = hiprtc();
     if (!rt.why.empty()) { log = rt.why; return GMMVI_ERR_HIP; }
-    std::string text = mode == MODE_HAND ? std::string(source) : std::string(kAutodiffPrelude) + source + "\n";
+    std::string text = kAutodiffPrelude;
+    if (source[strspn(source, " \t")] == '#') text += "\n#line 1\n";   // a directive has to begin its line; the numbers stay the user's
+    text += std::string(source) + "\n" + kSpecialText;
     if (mode == MODE_TAPE) {
         text += kTapeText;
     } else {

@@ -8,7 +8,9 @@ R"GMMVI_AD(
 //
 // Tie rules: fabs has tangent 0 at +-0; fmax and fmin take the first operand's tangent on a tie; comparisons look at the values
 // only, so a branch on a comparison differentiates the branch taken.  sqrt and rsqrt at 0 and log at 0 have infinite
-// derivatives, as in IEEE arithmetic.  There is no conversion from a dual to float: gmmvi_value(t) is the only way down.
+// derivatives, as in IEEE arithmetic.  lgamma has a NaN tangent at a <= 0; gmmvi_logaddexp has the tangents 1/2 and 1/2 on a tie;
+// gmmvi_sigmoid is exactly 1 or 0 with tangent 0 beyond the range of expf.  There is no conversion from a dual to float:
+// gmmvi_value(t) is the only way down.
 
 namespace gmmvi_ad {
 
@@ -138,13 +140,39 @@ GMMVI_AD_FN Dual pow(float a, const Dual& b) { return pow(Dual(a), b); }
 #define GMMVI_AD_ALIAS1(name) GMMVI_AD_FN Dual name##f(const Dual& a) { return name(a); }
 GMMVI_AD_ALIAS1(exp) GMMVI_AD_ALIAS1(expm1) GMMVI_AD_ALIAS1(log) GMMVI_AD_ALIAS1(log1p) GMMVI_AD_ALIAS1(sqrt) GMMVI_AD_ALIAS1(rsqrt)
 GMMVI_AD_ALIAS1(sin) GMMVI_AD_ALIAS1(cos) GMMVI_AD_ALIAS1(tan) GMMVI_AD_ALIAS1(tanh) GMMVI_AD_ALIAS1(atan) GMMVI_AD_ALIAS1(fabs)
-#undef GMMVI_AD_ALIAS1
 #define GMMVI_AD_ALIAS2(name)                                                              \
     GMMVI_AD_FN Dual name##f(const Dual& a, const Dual& b) { return name(a, b); }          \
     GMMVI_AD_FN Dual name##f(const Dual& a, float b) { return name(a, b); }                \
     GMMVI_AD_FN Dual name##f(float a, const Dual& b) { return name(a, b); }
 GMMVI_AD_ALIAS2(fmax) GMMVI_AD_ALIAS2(fmin) GMMVI_AD_ALIAS2(pow)
 #undef GMMVI_AD_ALIAS2
+
+// ---- special functions: the float functions of custom_target_special.inc, which custom_target.hip puts in front of this text ------
+// lgamma has the tangent digamma(a) da, hence NaN for a <= 0 (the value is still lgammaf's); lgammaf itself stays ROCm's float
+// function and takes no dual.  gmmvi_trigamma takes no dual either: there are no second derivatives.
+GMMVI_AD_FN Dual lgamma(const Dual& a) { return chain(::lgammaf(a.v), ::gmmvi_digamma(a.v), a); }
+GMMVI_AD_FN Dual erf(const Dual& a) { return chain(::erff(a.v), gmmvi_special::erf_partial(a.v), a); }
+GMMVI_AD_FN Dual erfc(const Dual& a) { return chain(::erfcf(a.v), -gmmvi_special::erf_partial(a.v), a); }
+GMMVI_AD_ALIAS1(erf) GMMVI_AD_ALIAS1(erfc)
+#undef GMMVI_AD_ALIAS1
+GMMVI_AD_FN Dual gmmvi_digamma(const Dual& a) { return chain(::gmmvi_digamma(a.v), ::gmmvi_trigamma(a.v), a); }
+// s sigmoid(-a), not s (1 - s), which cancels for large a
+GMMVI_AD_FN Dual gmmvi_sigmoid(const Dual& a) { const float s = ::gmmvi_sigmoid(a.v); return chain(s, s * ::gmmvi_sigmoid(-a.v), a); }
+GMMVI_AD_FN Dual gmmvi_softplus(const Dual& a) { return chain(::gmmvi_softplus(a.v), ::gmmvi_sigmoid(a.v), a); }
+GMMVI_AD_FN Dual gmmvi_log_sigmoid(const Dual& a) { return chain(::gmmvi_log_sigmoid(a.v), ::gmmvi_sigmoid(-a.v), a); }
+// tangents sigmoid(a - b) da + sigmoid(b - a) db: exactly 1/2 and 1/2 on a tie
+GMMVI_AD_FN Dual gmmvi_logaddexp(const Dual& a, const Dual& b) {
+    Dual r; r.v = ::gmmvi_logaddexp(a.v, b.v);
+    const float pa = gmmvi_special::logaddexp_partial(a.v, b.v), pb = gmmvi_special::logaddexp_partial(b.v, a.v);
+    GMMVI_AD_EACH r.d[j] = pa * a.d[j] + pb * b.d[j];
+    return r;
+}
+GMMVI_AD_FN Dual gmmvi_logaddexp(const Dual& a, float b) {
+    return chain(::gmmvi_logaddexp(a.v, b), gmmvi_special::logaddexp_partial(a.v, b), a);
+}
+GMMVI_AD_FN Dual gmmvi_logaddexp(float a, const Dual& b) {
+    return chain(::gmmvi_logaddexp(a, b.v), gmmvi_special::logaddexp_partial(b.v, a), b);
+}
 
 GMMVI_AD_FN float gmmvi_value(const Dual& a) { return a.v; }
 

@@ -177,13 +177,34 @@ GMMVI_TAPE_FN Var pow(float a, const Var& b) { return pow(Var(a), b); }
 GMMVI_TAPE_ALIAS1(exp) GMMVI_TAPE_ALIAS1(expm1) GMMVI_TAPE_ALIAS1(log) GMMVI_TAPE_ALIAS1(log1p) GMMVI_TAPE_ALIAS1(sqrt)
 GMMVI_TAPE_ALIAS1(rsqrt) GMMVI_TAPE_ALIAS1(sin) GMMVI_TAPE_ALIAS1(cos) GMMVI_TAPE_ALIAS1(tan) GMMVI_TAPE_ALIAS1(tanh)
 GMMVI_TAPE_ALIAS1(atan) GMMVI_TAPE_ALIAS1(fabs)
-#undef GMMVI_TAPE_ALIAS1
 #define GMMVI_TAPE_ALIAS2(name)                                                          \
     GMMVI_TAPE_FN Var name##f(const Var& a, const Var& b) { return name(a, b); }         \
     GMMVI_TAPE_FN Var name##f(const Var& a, float b) { return name(a, b); }              \
     GMMVI_TAPE_FN Var name##f(float a, const Var& b) { return name(a, b); }
 GMMVI_TAPE_ALIAS2(fmax) GMMVI_TAPE_ALIAS2(fmin) GMMVI_TAPE_ALIAS2(pow)
 #undef GMMVI_TAPE_ALIAS2
+
+// ---- special functions: the float functions of custom_target_special.inc, which custom_target.hip puts in front of this text; one
+// record per call, the partials of the forward mode (lgamma: digamma(a), NaN for a <= 0; gmmvi_logaddexp: 1/2 and 1/2 on a tie) -----
+GMMVI_TAPE_FN Var lgamma(const Var& a) { return node(::lgammaf(a.v), a, ::gmmvi_digamma(a.v)); }
+GMMVI_TAPE_FN Var erf(const Var& a) { return node(::erff(a.v), a, gmmvi_special::erf_partial(a.v)); }
+GMMVI_TAPE_FN Var erfc(const Var& a) { return node(::erfcf(a.v), a, -gmmvi_special::erf_partial(a.v)); }
+GMMVI_TAPE_ALIAS1(erf) GMMVI_TAPE_ALIAS1(erfc)
+#undef GMMVI_TAPE_ALIAS1
+GMMVI_TAPE_FN Var gmmvi_digamma(const Var& a) { return node(::gmmvi_digamma(a.v), a, ::gmmvi_trigamma(a.v)); }
+GMMVI_TAPE_FN Var gmmvi_sigmoid(const Var& a) { const float s = ::gmmvi_sigmoid(a.v); return node(s, a, s * ::gmmvi_sigmoid(-a.v)); }
+GMMVI_TAPE_FN Var gmmvi_softplus(const Var& a) { return node(::gmmvi_softplus(a.v), a, ::gmmvi_sigmoid(a.v)); }
+GMMVI_TAPE_FN Var gmmvi_log_sigmoid(const Var& a) { return node(::gmmvi_log_sigmoid(a.v), a, ::gmmvi_sigmoid(-a.v)); }
+GMMVI_TAPE_FN Var gmmvi_logaddexp(const Var& a, const Var& b) {
+    return node(::gmmvi_logaddexp(a.v, b.v), a, gmmvi_special::logaddexp_partial(a.v, b.v), b,
+                gmmvi_special::logaddexp_partial(b.v, a.v));
+}
+GMMVI_TAPE_FN Var gmmvi_logaddexp(const Var& a, float b) {
+    return node(::gmmvi_logaddexp(a.v, b), a, gmmvi_special::logaddexp_partial(a.v, b));
+}
+GMMVI_TAPE_FN Var gmmvi_logaddexp(float a, const Var& b) {
+    return node(::gmmvi_logaddexp(a, b.v), b, gmmvi_special::logaddexp_partial(b.v, a));
+}
 
 GMMVI_TAPE_FN float gmmvi_value(const Var& a) { return a.v; }
 

@@ -1,9 +1,11 @@
 // gmmvi_tape_probe (include/gmmvi_hip.h): one operation of the tape's number type (custom_target_tape.inc, its raw-string
 // delimiters taken off by the Makefile, without the kernels, which need a user's function), run on a tape in host memory.  The
-// operations and their order are those of autodiff_probe.hip.  Host code only.
+// operations and their order are those of autodiff_probe.hip, gmmvi_tape_probe_special's those of
+// gmmvi_autodiff_probe_special.  Host code only.
 #include "common.h"
 
 #define GMMVI_TAPE_NO_KERNELS
+#include "build/custom_target_special_text.inc"
 #include "build/custom_target_tape_text.inc"
 
 namespace {
@@ -35,6 +37,23 @@ Var flag(bool c) { return Var(c ? 1.f : 0.f); }
 constexpr int kBase = __COUNTER__ + 1;
 }  // namespace
 
+// what both probes report of the operation's result and of the one record it made
+static int report(const Var& r, const gmmvi_tape::Rec4* rec, float* value, float* pa, float* pb, int* records) {
+    *value = r.v;
+    *records = gmmvi_tape::count();
+    *pa = *pb = 0.f;
+    // the partials of the operation's one record, by the id of the parent they belong to (a is node 0, b is node 1)
+    if (*records == 1) {
+        const int ids[2] = {rec[0].x, rec[0].y};
+        const float partials[2] = {gmmvi_tape::bits_float(rec[0].z), gmmvi_tape::bits_float(rec[0].w)};
+        for (int j = 0; j < 2; ++j) {
+            if (ids[j] == 0) *pa += partials[j];
+            if (ids[j] == 1) *pb += partials[j];
+        }
+    }
+    return GMMVI_OK;
+}
+
 extern "C" int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb,
                                 int* records) {
     if (!value || !pa || !pb || !records)
@@ -57,17 +76,34 @@ extern "C" int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_
         default:
             return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe: unknown operation " + std::to_string(op));
     }
-    *value = r.v;
-    *records = gmmvi_tape::count();
-    *pa = *pb = 0.f;
-    // the partials of the operation's one record, by the id of the parent they belong to (a is node 0, b is node 1)
-    if (*records == 1) {
-        const int ids[2] = {rec[0].x, rec[0].y};
-        const float partials[2] = {gmmvi_tape::bits_float(rec[0].z), gmmvi_tape::bits_float(rec[0].w)};
-        for (int j = 0; j < 2; ++j) {
-            if (ids[j] == 0) *pa += partials[j];
-            if (ids[j] == 1) *pb += partials[j];
-        }
+    return report(r, rec, value, pa, pb, records);
+}
+
+extern "C" int gmmvi_tape_probe_special(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb,
+                                        int* records) {
+    if (!value || !pa || !pb || !records)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_special: value, pa, pb and records must not be NULL");
+    constexpr int kBase = __COUNTER__ + 1;
+    constexpr int kCap = 4;
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, 2};   // stride 1, D = 2
+    gmmvi_tape::count() = 0;
+    const Var A = a_is_const ? Var(a) : Var(a, 0), B = b_is_const ? Var(b) : Var(b, 1);
+    Var r;
+    switch (op) {
+        case __COUNTER__ - kBase: r = lgamma(A); break;                    // lgammaf stays a float function
+        PROBE_UNARY(erf) PROBE_UNARY(erfc)
+        case __COUNTER__ - kBase: r = gmmvi_digamma(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_sigmoid(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_softplus(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_log_sigmoid(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_logaddexp(A, B); break;
+        case __COUNTER__ - kBase: r = gmmvi_logaddexp(A, b); break;
+        case __COUNTER__ - kBase: r = gmmvi_logaddexp(a, B); break;
+        case __COUNTER__ - kBase: r = Var(gmmvi_trigamma(a)); break;       // a float function only: a constant
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_special: unknown operation " + std::to_string(op));
     }
-    return GMMVI_OK;
+    return report(r, rec, value, pa, pb, records);
 }

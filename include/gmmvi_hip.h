@@ -350,12 +350,34 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  *   - < <= > >= == !=, decided on the values;
  *   - exp expm1 log log1p sqrt rsqrt sin cos tan tanh atan fabs fmax fmin, pow(T, float) and pow(T, T), each also under its
  *     f-suffixed name (expf, ...);
+ *   - lgamma, and erf erfc, these two also under their f-suffixed names: the values are ROCm's lgammaf, erff and erfcf, the
+ *     derivatives gmmvi_digamma(a) and +-2 / sqrt(pi) exp(-a^2).  lgammaf itself stays a float function: on a T it is a
+ *     compile error, spell it lgamma;
+ *   - gmmvi_digamma(t), gmmvi_sigmoid(t), gmmvi_softplus(t), gmmvi_log_sigmoid(t), and gmmvi_logaddexp between T and T, T and
+ *     float, float and T (below);
  *   - gmmvi_value(t): the float value of a float and of a dual.
  * A float converts to a T (a constant: all tangents 0); a T does not convert to float, so a function outside this list, such
- * as lgammaf or erff, on a T is a compile error (GMMVI_ERR_ARG with the compiler log, as for any source).
+ * as tgammaf, erfinvf or lgammaf, on a T is a compile error (GMMVI_ERR_ARG with the compiler log, as for any source).
+ * The library's float functions (csrc/custom_target_special.inc; plain C++, host and device).  In every mode, the hand-written
+ * one included, they are declared in front of the source's first line, on that line (where that line begins with a directive, on
+ * a line of their own, followed by a line directive that keeps the numbers the user's), and defined behind the source; a source
+ * may call them on a float, and must not define these or any other gmmvi_ name:
+ *   - float gmmvi_digamma(float x): psi(x) for x > 0, by the recurrence up to x >= 6 and the asymptotic series; x <= 0 and NaN
+ *     give NaN (no reflection formula);
+ *   - float gmmvi_trigamma(float x): psi'(x), the same way and with the same domain.  It takes a float only: there are no
+ *     second derivatives, so gmmvi_trigamma of a T is a compile error;
+ *   - float gmmvi_sigmoid(float x): 1 / (1 + e^-x), from e^-|x| alone: exactly 1 and 0 beyond the range of expf;
+ *   - float gmmvi_softplus(float x): log(1 + e^x) = fmax(x, 0) + log1p(exp(-|x|));
+ *   - float gmmvi_log_sigmoid(float x): -gmmvi_softplus(-x);
+ *   - float gmmvi_logaddexp(float a, float b): log(e^a + e^b) = max + log1p(exp(-|a - b|)); a == b, equal infinities
+ *     included, gives a + ln 2 and no NaN.
+ * On a T: gmmvi_digamma has the derivative gmmvi_trigamma(a); gmmvi_sigmoid s * sigmoid(-a) (not s (1 - s), which cancels for
+ * large a); gmmvi_softplus sigmoid(a); gmmvi_log_sigmoid sigmoid(-a); gmmvi_logaddexp sigmoid(a - b) and sigmoid(b - a).
  * Tie rules: fabs has tangent 0 at +-0; fmax and fmin take the first operand's tangent on a tie; a branch on a comparison
  * differentiates the branch taken.  pow(T, T) takes no part of ln(a) in a direction in which the exponent does not move;
- * sqrt, rsqrt and log at 0 have the infinite derivatives of IEEE arithmetic.
+ * sqrt, rsqrt and log at 0 have the infinite derivatives of IEEE arithmetic.  lgamma of a T has a NaN derivative at a <= 0
+ * (digamma's; the value is still lgammaf's); gmmvi_logaddexp has the derivatives exactly 1/2 and 1/2 on a tie; gmmvi_sigmoid
+ * beyond the range of expf is exactly 1 or 0 with derivative exactly 0.
  * The gradient takes ceil(D / W) passes of the dual instantiation, W = GMMVI_CUSTOM_AUTODIFF_TANGENTS, pass `first` writing
  * grad[first + j] for first + j < D; the value is that of the first pass.  That is ceil(D / W) * (1 + W) value evaluations per
  * sample, so a gradient call through such a handle is capped at GMMVI_CUSTOM_AUTODIFF_MAX_DIM; a value call is not. */
@@ -372,6 +394,10 @@ int gmmvi_custom_target_compile_autodiff(gmmvi_ctx* ctx, const char* source, gmm
  * operations in the order of csrc/autodiff_probe.hip (gmmvi_amd/_lib.py AUTODIFF_OPS names them); comparisons give 1 or 0
  * with tangent 0.  An unknown op or a NULL output: GMMVI_ERR_ARG. */
 int gmmvi_autodiff_probe(int op, float a, float da, float b, float db, float* value, float* tangent);
+/* The same for the special functions, a list of their own (gmmvi_amd/_lib.py SPECIAL_OPS names them in index order): lgamma;
+ * erf and erfc, each under both spellings; gmmvi_digamma, gmmvi_sigmoid, gmmvi_softplus, gmmvi_log_sigmoid, gmmvi_logaddexp in its
+ * three operand forms, and gmmvi_trigamma of the float a (a constant: tangent 0). */
+int gmmvi_autodiff_probe_special(int op, float a, float da, float b, float db, float* value, float* tangent);
 
 /* ---- user-defined targets summed over a data set --------------------------------------------------------------------------------
  * Posteriors of the shape  log p(x) = log prior(x) + sum over the data rows r of log p(data_r | x):  the source defines one
@@ -516,6 +542,9 @@ int gmmvi_target_custom_tape(gmmvi_ctx* ctx, const gmmvi_custom_target* target, 
  * (0 where it recorded none: a constant or float operand, a comparison, gmmvi_value); *records: the records it made.  An
  * unknown op or a NULL output: GMMVI_ERR_ARG. */
 int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb, int* records);
+/* The same for the special functions: op indexes the operations in the order of gmmvi_autodiff_probe_special. */
+int gmmvi_tape_probe_special(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb,
+                             int* records);
 
 /* ---- targets summed over a data set, differentiated on a tape ------------------------------------------------------------------
  * The source of the data mode, unchanged (gmmvi_user_row and gmmvi_user_prior, templates over the number type; compiled with
