@@ -69,7 +69,7 @@ struct gmmvi_ctx {
     void* defer_ws = nullptr;    // partials of a deferred merge (ctx->ws is reused by the launches in between)
     size_t defer_bytes = 0;
     void* comm = nullptr;        // ncclComm_t
-    std::vector<gmmvi_custom_target*> custom_targets;   // loaded user-defined targets (custom_target.hip), released with the context
+    std::vector<gmmvi_custom_target*> custom_targets;   // loaded user-defined targets (custom_compile.hip), released with the context
     int n_ranks = 1, rank = 0;
     int num_cus = 256;
     std::vector<std::pair<const void*, size_t>> lds_limits;   // (kernel, dynamic-LDS limit set on this context's device): gmmvi_ensure_dynamic_lds
@@ -123,7 +123,7 @@ int gmmvi_ws_reserve(gmmvi_ctx* ctx, size_t nbytes);
 // api.hip: raises the dynamic-LDS limit of kernel `func` to `bytes` unless this context has already set as much (the attribute is
 // per device, so it is remembered per context); nothing to do up to the 64 KB every kernel may use
 int gmmvi_ensure_dynamic_lds(gmmvi_ctx* ctx, const void* func, size_t bytes);
-// custom_target.hip: unloads every user-defined target of the context (gmmvi_ctx_destroy)
+// custom_compile.hip: unloads every user-defined target of the context (gmmvi_ctx_destroy)
 void gmmvi_custom_targets_destroy(gmmvi_ctx* ctx);
 // density.hip: component blocks in the register-path layout (Pack<padded D>, D <= 64) regardless of the blocked threshold
 int gmmvi_pack_register_layout(gmmvi_ctx* ctx, int K, int D, const float* means_dev, const float* chols_dev, float* packed_dev);

@@ -39,7 +39,47 @@ from .lnpdf import LNPDF
 from .minibatch_stream import MinibatchLNPDF
 
 
-class DeviceLNPDF(LNPDF):
+def _checked_dimension(num_dimensions):
+    if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
+        raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
+    return int(num_dimensions)
+
+
+def _host_params(params):
+    """``params`` as a contiguous one-dimensional fp32 host array (None stays None), or ValueError; touches no device."""
+    if params is not None:
+        params = np.ascontiguousarray(np.asarray(params.numpy() if hasattr(params, "numpy") else params), np.float32)
+        if params.ndim != 1:
+            raise ValueError(f"params must be one-dimensional, got shape {params.shape}")
+    return params
+
+
+class _DeviceTarget:
+    """What the classes of this module share; the tape options and the rule of the first gradient call: the two tape classes."""
+
+    def get_num_dimensions(self):
+        return self._num_dimensions
+
+    def _x(self, x):
+        x = self.ctx.asarray(x)
+        if len(x.shape) != 2 or x.shape[1] != self._num_dimensions:
+            raise ValueError(f"samples: expected [n, {self._num_dimensions}], got {x.shape}")
+        return x
+
+    def _set_tape_options(self, tape_capacity, scratch_bytes):
+        for name, value in (("tape_capacity", tape_capacity), ("scratch_bytes", scratch_bytes)):
+            if value is not None and (int(value) != value or int(value) < 1):
+                raise ValueError(f"{name} must be a positive integer or None, got {value!r}")
+        self.tape_capacity = 0 if tape_capacity is None else int(tape_capacity)
+        self.scratch_bytes = 0 if scratch_bytes is None else int(scratch_bytes)
+
+    def _tape_keywords(self, want_grad=True):
+        # the asked-for capacity sizes the first gradient launch; afterwards the handle knows what the target needs
+        first = want_grad and self.tape_capacity and hip_ops.custom_tape_length(self.ctx, self._handle, self._num_dimensions) == 0
+        return {"tape_capacity": self.tape_capacity if first else 0, "scratch_bytes": self.scratch_bytes}
+
+
+class DeviceLNPDF(_DeviceTarget, LNPDF):
     """``DeviceLNPDF(source, num_dimensions, params=None, has_gradient=True)``; pass it as ``config['target_fn']``.
 
     params: the target's own numbers (1-D, fp32 on the device; ``None``: the function gets a null pointer).
@@ -54,14 +94,9 @@ class DeviceLNPDF(LNPDF):
 
     def __init__(self, source, num_dimensions, params=None, has_gradient=True):
         super().__init__(use_log_density_and_grad=True)
-        if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
-            raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
-        if int(num_dimensions) > _lib.MAX_DIM_DIAG:
+        if _checked_dimension(num_dimensions) > _lib.MAX_DIM_DIAG:
             raise ValueError(f"num_dimensions must be <= {_lib.MAX_DIM_DIAG}, got {num_dimensions}")
-        if params is not None:
-            params = np.ascontiguousarray(np.asarray(params.numpy() if hasattr(params, "numpy") else params), np.float32)
-            if params.ndim != 1:
-                raise ValueError(f"params must be one-dimensional, got shape {params.shape}")
+        params = _host_params(params)
         self.ctx = get_context()
         self.source = str(source)
         self.has_gradient = bool(has_gradient)
@@ -71,15 +106,6 @@ class DeviceLNPDF(LNPDF):
 
     def _compile(self):
         return hip_ops.custom_target_compile(self.ctx, self.source)
-
-    def get_num_dimensions(self):
-        return self._num_dimensions
-
-    def _x(self, x):
-        x = self.ctx.asarray(x)
-        if len(x.shape) != 2 or x.shape[1] != self._num_dimensions:
-            raise ValueError(f"samples: expected [n, {self._num_dimensions}], got {x.shape}")
-        return x
 
     def log_density(self, x):
         return hip_ops.target_custom(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=False)[0]
@@ -140,11 +166,7 @@ class DeviceTapeLNPDF(DeviceLNPDF):
         return object.__new__(cls)
 
     def __init__(self, source, num_dimensions, params=None, tape_capacity=None, scratch_bytes=None):
-        for name, value in (("tape_capacity", tape_capacity), ("scratch_bytes", scratch_bytes)):
-            if value is not None and (int(value) != value or int(value) < 1):
-                raise ValueError(f"{name} must be a positive integer or None, got {value!r}")
-        self.tape_capacity = 0 if tape_capacity is None else int(tape_capacity)
-        self.scratch_bytes = 0 if scratch_bytes is None else int(scratch_bytes)
+        self._set_tape_options(tape_capacity, scratch_bytes)
         super().__init__(source, num_dimensions, params, has_gradient=True)
 
     def _compile(self):
@@ -154,13 +176,10 @@ class DeviceTapeLNPDF(DeviceLNPDF):
         return hip_ops.target_custom_tape(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=False)[0]
 
     def log_density_and_grad(self, x):
-        # the asked-for capacity sizes the first launch; afterwards the handle knows what the target needs
-        first = self.tape_capacity and hip_ops.custom_tape_length(self.ctx, self._handle, self._num_dimensions) == 0
-        return hip_ops.target_custom_tape(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=True,
-                                          tape_capacity=self.tape_capacity if first else 0, scratch_bytes=self.scratch_bytes)
+        return hip_ops.target_custom_tape(self.ctx, self._handle, self._params_dev, self._x(x), want_grad=True, **self._tape_keywords())
 
 
-class _DeviceDataTarget(MinibatchLNPDF):
+class _DeviceDataTarget(_DeviceTarget, MinibatchLNPDF):
     """What ``DeviceDataLNPDF`` and ``DeviceDataTapeLNPDF`` share: the argument checks, the upload, the call counter of
     ``MinibatchLNPDF`` and ``log_density_full``.  A subclass names its compile mode, checks the dimension and launches."""
 
@@ -187,18 +206,13 @@ class _DeviceDataTarget(MinibatchLNPDF):
         super().__init__(seed)
         if use_own_batch_per_sample and batch_size is None:
             raise ValueError("use_own_batch_per_sample needs a batch_size: without one every sample sees all rows")
-        if int(num_dimensions) != num_dimensions or int(num_dimensions) < 1:
-            raise ValueError(f"num_dimensions must be a positive integer, got {num_dimensions!r}")
-        self._check_dimension(int(num_dimensions))
+        self._check_dimension(_checked_dimension(num_dimensions))
         data = np.ascontiguousarray(np.asarray(data.numpy() if hasattr(data, "numpy") else data), np.float32)
         if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] < 1:
             raise ValueError(f"data must be two-dimensional [rows >= 1, floats per row >= 1], got shape {data.shape}")
         if batch_size is not None and (int(batch_size) != batch_size or not 1 <= int(batch_size) <= data.shape[0]):
             raise ValueError(f"batch_size must be an integer in 1..{data.shape[0]} (the rows of data) or None, got {batch_size!r}")
-        if params is not None:
-            params = np.ascontiguousarray(np.asarray(params.numpy() if hasattr(params, "numpy") else params), np.float32)
-            if params.ndim != 1:
-                raise ValueError(f"params must be one-dimensional, got shape {params.shape}")
+        params = _host_params(params)
         if eval_sets is not None:
             if not isinstance(eval_sets, dict):
                 raise ValueError(f"eval_sets must be a dict name -> [rows, {data.shape[1]}] array or None, got {type(eval_sets)}")
@@ -215,15 +229,6 @@ class _DeviceDataTarget(MinibatchLNPDF):
         self._data_dev = self.ctx.asarray(data)
         self._params_dev = None if params is None or params.size == 0 else self.ctx.asarray(params)
         self._handle = hip_ops.custom_target_compile(self.ctx, self.source, mode=self._mode)
-
-    def get_num_dimensions(self):
-        return self._num_dimensions
-
-    def _x(self, x):
-        x = self.ctx.asarray(x)
-        if len(x.shape) != 2 or x.shape[1] != self._num_dimensions:
-            raise ValueError(f"samples: expected [n, {self._num_dimensions}], got {x.shape}")
-        return x
 
     def _batch_keywords(self, batch_size):
         """What a subclass adds to its ``hip_ops`` call for the row list: nothing for a shared batch or the full data."""
@@ -335,11 +340,7 @@ class DeviceDataTapeLNPDF(_DeviceDataTarget):
 
     def __init__(self, source, num_dimensions, data, params=None, batch_size=None, seed=0, use_own_batch_per_sample=False,
                  tape_capacity=None, scratch_bytes=None, eval_sets=None, report_waic=False):
-        for name, value in (("tape_capacity", tape_capacity), ("scratch_bytes", scratch_bytes)):
-            if value is not None and (int(value) != value or int(value) < 1):
-                raise ValueError(f"{name} must be a positive integer or None, got {value!r}")
-        self.tape_capacity = 0 if tape_capacity is None else int(tape_capacity)
-        self.scratch_bytes = 0 if scratch_bytes is None else int(scratch_bytes)
+        self._set_tape_options(tape_capacity, scratch_bytes)
         super().__init__(source, num_dimensions, data, params, batch_size, seed, use_own_batch_per_sample, eval_sets, report_waic)
 
     def _check_dimension(self, num_dimensions):
@@ -347,9 +348,6 @@ class DeviceDataTapeLNPDF(_DeviceDataTarget):
             raise ValueError(f"num_dimensions must be <= {_lib.MAX_DIM_DIAG}, got {num_dimensions}")
 
     def _target_call(self, x, want_grad, batch_size, call):
-        # the asked-for capacity sizes the first gradient launch; afterwards the handle knows what the target needs
-        first = want_grad and self.tape_capacity and hip_ops.custom_tape_length(self.ctx, self._handle, self._num_dimensions) == 0
         return hip_ops.target_custom_data_tape(self.ctx, self._handle, self._params_dev, self._data_dev, x, want_grad=want_grad,
-                                               batch_size=batch_size, seed=self.seed, call=call,
-                                               tape_capacity=self.tape_capacity if first else 0, scratch_bytes=self.scratch_bytes,
+                                               batch_size=batch_size, seed=self.seed, call=call, **self._tape_keywords(want_grad),
                                                **self._batch_keywords(batch_size))

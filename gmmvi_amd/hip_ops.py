@@ -92,49 +92,50 @@ def target_planar(ctx, prior_std, goals, likelihood_std, x, want_grad=True):
     return lp, grad
 
 
-def custom_target_check(source, arch="gfx950"):
-    """Compiles a user target's source behind the wrapper kernels for ``arch`` (csrc/custom_target.hip) without a device.
-    -> (status, compiler log): 0 when it compiles, GMMVI_ERR_ARG (-2) with the log otherwise."""
+def _ptr(a):
+    return None if a is None else a.ptr
+
+
+def _custom_entry(lib, stem, mode):
+    """The entry of compile mode ``mode`` among ``stem``, ``stem``_autodiff, ..., one per member of CUSTOM_TARGET_MODES."""
+    return getattr(lib, stem if mode == "hand" else f"{stem}_{mode}")
+
+
+def _custom_target_check(mode, source, arch):
     import ctypes as C
     log = C.create_string_buffer(1 << 16)
-    rc = _lib.load().gmmvi_custom_target_check(str(source).encode(), str(arch).encode(), log, len(log))
+    rc = _custom_entry(_lib.load(), "gmmvi_custom_target_check", mode)(str(source).encode(), str(arch).encode(), log, len(log))
     return int(rc), log.value.decode(errors="replace")
+
+
+def custom_target_check(source, arch="gfx950"):
+    """Compiles a user target's source behind the wrapper kernels for ``arch`` (csrc/custom_compile.hip) without a device.
+    -> (status, compiler log): 0 when it compiles, GMMVI_ERR_ARG (-2) with the log otherwise."""
+    return _custom_target_check("hand", source, arch)
 
 
 def custom_target_check_autodiff(source, arch="gfx950"):
     """custom_target_check for a source that defines ``gmmvi_user_density`` (the log density only; the library's dual-number
     text differentiates it).  -> (status, compiler log)."""
-    import ctypes as C
-    log = C.create_string_buffer(1 << 16)
-    rc = _lib.load().gmmvi_custom_target_check_autodiff(str(source).encode(), str(arch).encode(), log, len(log))
-    return int(rc), log.value.decode(errors="replace")
+    return _custom_target_check("autodiff", source, arch)
 
 
 def custom_target_check_data(source, arch="gfx950"):
     """custom_target_check for a source that defines ``gmmvi_user_row`` and ``gmmvi_user_prior`` (a target summed over a data set,
     csrc/custom_target_data.inc).  -> (status, compiler log)."""
-    import ctypes as C
-    log = C.create_string_buffer(1 << 16)
-    rc = _lib.load().gmmvi_custom_target_check_data(str(source).encode(), str(arch).encode(), log, len(log))
-    return int(rc), log.value.decode(errors="replace")
+    return _custom_target_check("data", source, arch)
 
 
 def custom_target_check_tape(source, arch="gfx950"):
     """custom_target_check for a source that defines ``gmmvi_user_density``, compiled for the tape mode (reverse-mode
     differentiation, csrc/custom_target_tape.inc).  -> (status, compiler log)."""
-    import ctypes as C
-    log = C.create_string_buffer(1 << 16)
-    rc = _lib.load().gmmvi_custom_target_check_tape(str(source).encode(), str(arch).encode(), log, len(log))
-    return int(rc), log.value.decode(errors="replace")
+    return _custom_target_check("tape", source, arch)
 
 
 def custom_target_check_data_tape(source, arch="gfx950"):
     """custom_target_check for a source that defines ``gmmvi_user_row`` and ``gmmvi_user_prior``, compiled for the data mode with
     reverse-mode gradients (csrc/custom_target_data_tape.inc).  -> (status, compiler log)."""
-    import ctypes as C
-    log = C.create_string_buffer(1 << 16)
-    rc = _lib.load().gmmvi_custom_target_check_data_tape(str(source).encode(), str(arch).encode(), log, len(log))
-    return int(rc), log.value.decode(errors="replace")
+    return _custom_target_check("data_tape", source, arch)
 
 
 def custom_data_tape_plan(n, rows, d, capacity, chunks_requested=0, scratch_bytes=0):
@@ -228,29 +229,58 @@ def custom_target_compile(ctx, source, autodiff=False, mode=None):
     if mode not in CUSTOM_TARGET_MODES:
         raise ValueError(f"mode: expected one of {CUSTOM_TARGET_MODES}, got {mode!r}")
     h = C.c_void_p()
-    compile_fn = {"hand": ctx.lib.gmmvi_custom_target_compile, "autodiff": ctx.lib.gmmvi_custom_target_compile_autodiff,
-                  "data": ctx.lib.gmmvi_custom_target_compile_data, "tape": ctx.lib.gmmvi_custom_target_compile_tape,
-                  "data_tape": ctx.lib.gmmvi_custom_target_compile_data_tape}[mode]
-    ctx.check(compile_fn(ctx.handle, str(source).encode(), C.byref(h)))
+    ctx.check(_custom_entry(ctx.lib, "gmmvi_custom_target_compile", mode)(ctx.handle, str(source).encode(), C.byref(h)))
     return CustomTarget(ctx, h)
+
+
+def _custom_arguments(handle, x, params, rows=None, predictive=False):
+    """The host checks of every launcher of a user target, in the order they have always had: the handle, x [n, D], for a
+    launcher that takes one its row array [rows, C] ("rows" and not empty for the predictive density, else "data"), then params
+    (1-D or None) -> (n, D) or (n, D, rows, C)."""
+    if not isinstance(handle, CustomTarget):
+        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
+    if predictive and len(x.shape) != 2:
+        raise ValueError(f"x: expected a two-dimensional array, got {x.shape}")
+    n, d = shapes = x.shape
+    _req(x, (n, d), name="x")
+    if rows is not None:
+        name = "rows" if predictive else "data"
+        if len(rows.shape) != 2:
+            raise ValueError(f"{name}: expected a two-dimensional array, got {rows.shape}")
+        _req(rows, tuple(rows.shape), name=name)
+        shapes = (n, d) + tuple(rows.shape)
+        if predictive and (n < 1 or rows.shape[0] < 1):
+            raise ValueError(f"the predictive density needs at least one sample and one row, got {n} and {rows.shape[0]}")
+    if params is not None:
+        if len(params.shape) != 1:
+            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
+        _req(params, params.shape, name="params")
+    return shapes
 
 
 def target_custom(ctx, handle, params, x, want_grad=True, route=0):
     """User target ``handle`` on x [n, D] (csrc/custom_target.hip).  params: the target's 1-D device array or None; route: 0
     auto, 1 staged (LDS), 2 direct.  -> (lp [n], grad [n, D] or None)."""
-    if not isinstance(handle, CustomTarget):
-        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
-    n, d = x.shape
-    _req(x, (n, d), name="x")
-    if params is not None:
-        if len(params.shape) != 1:
-            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
-        _req(params, params.shape, name="params")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
+    n, d = _custom_arguments(handle, x, params)
+    lp, grad = ctx.empty((n,)), ctx.empty((n, d)) if want_grad else None
     if n > 0:
-        ctx.check(ctx.lib.gmmvi_target_custom(ctx.handle, handle.handle, d, None if params is None else params.ptr, x.ptr, n,
-                                              lp.ptr, None if grad is None else grad.ptr, int(route)))
+        ctx.check(ctx.lib.gmmvi_target_custom(ctx.handle, handle.handle, d, _ptr(params), x.ptr, n, lp.ptr, _ptr(grad), int(route)))
+    return lp, grad
+
+
+def _target_custom_data(ctx, stem, handle, params, data, x, want_grad, batch_size, seed, call, chunks, own_batches, *tail):
+    """What ``target_custom_data`` and ``target_custom_data_tape`` share: the checks, one argument list, and the choice between the
+    entry ``stem``, which takes the minibatch flag and B, and its ``_own_batches`` twin, which takes B alone.  tail: what the
+    entry takes behind chunks."""
+    if own_batches and batch_size is None:
+        raise ValueError("own_batches needs a batch_size: the full-data row list is the same for every sample")
+    n, d, t, c = _custom_arguments(handle, x, params, data)
+    lp, grad = ctx.empty((n,)), ctx.empty((n, d)) if want_grad else None
+    if n > 0:
+        entry = getattr(ctx.lib, stem + "_own_batches" if own_batches else stem)
+        batch = (int(batch_size),) if own_batches else (0, t) if batch_size is None else (1, int(batch_size))
+        ctx.check(entry(ctx.handle, handle.handle, d, _ptr(params), data.ptr, t, c, *batch, int(seed) & 0xFFFFFFFFFFFFFFFF,
+                        int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, _ptr(grad), int(chunks), *tail))
     return lp, grad
 
 
@@ -260,32 +290,8 @@ def target_custom_data(ctx, handle, params, data, x, want_grad=True, batch_size=
     with s = T / batch_size, one batch shared by all samples or, with own_batches, a batch of its own for every sample
     (``minibatch_stream.data_minibatch_rows_per_sample``; gmmvi_target_custom_data_own_batches).  chunks: 0 lets the library plan
     the launch, a positive number forces that many row chunks.  -> (lp [n], grad [n, D] or None)."""
-    if own_batches and batch_size is None:
-        raise ValueError("own_batches needs a batch_size: the full-data row list is the same for every sample")
-    if not isinstance(handle, CustomTarget):
-        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
-    n, d = x.shape
-    _req(x, (n, d), name="x")
-    if len(data.shape) != 2:
-        raise ValueError(f"data: expected a two-dimensional array, got {data.shape}")
-    t, c = data.shape
-    _req(data, (t, c), name="data")
-    if params is not None:
-        if len(params.shape) != 1:
-            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
-        _req(params, params.shape, name="params")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0 and own_batches:
-        ctx.check(ctx.lib.gmmvi_target_custom_data_own_batches(
-            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c, int(batch_size),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks)))
-    elif n > 0:
-        ctx.check(ctx.lib.gmmvi_target_custom_data(
-            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c,
-            0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks)))
-    return lp, grad
+    return _target_custom_data(ctx, "gmmvi_target_custom_data", handle, params, data, x, want_grad, batch_size, seed, call, chunks,
+                               own_batches)
 
 
 def target_custom_tape(ctx, handle, params, x, want_grad=True, tape_capacity=0, scratch_bytes=0):
@@ -293,20 +299,11 @@ def target_custom_tape(ctx, handle, params, x, want_grad=True, tape_capacity=0, 
     and one backward sweep per sample.  tape_capacity: records per lane, 0 what the handle has needed at this D so far;
     scratch_bytes: the budget of the tape scratch, 0 the default.  A gradient call synchronises the stream.
     -> (lp [n], grad [n, D] or None)."""
-    if not isinstance(handle, CustomTarget):
-        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
-    n, d = x.shape
-    _req(x, (n, d), name="x")
-    if params is not None:
-        if len(params.shape) != 1:
-            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
-        _req(params, params.shape, name="params")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
+    n, d = _custom_arguments(handle, x, params)
+    lp, grad = ctx.empty((n,)), ctx.empty((n, d)) if want_grad else None
     if n > 0:
-        ctx.check(ctx.lib.gmmvi_target_custom_tape(ctx.handle, handle.handle, d, None if params is None else params.ptr, x.ptr, n,
-                                                   lp.ptr, None if grad is None else grad.ptr, int(tape_capacity),
-                                                   int(scratch_bytes)))
+        ctx.check(ctx.lib.gmmvi_target_custom_tape(ctx.handle, handle.handle, d, _ptr(params), x.ptr, n, lp.ptr, _ptr(grad),
+                                                   int(tape_capacity), int(scratch_bytes)))
     return lp, grad
 
 
@@ -317,34 +314,8 @@ def target_custom_data_tape(ctx, handle, params, data, x, want_grad=True, batch_
     tape_capacity: records per lane, 0 what the handle has needed at this D so far; scratch_bytes: the budget of the tapes and
     accumulators, 0 the default.  own_batches: as for ``target_custom_data`` (gmmvi_target_custom_data_tape_own_batches).  A
     gradient call synchronises the stream.  -> (lp [n], grad [n, D] or None)."""
-    if own_batches and batch_size is None:
-        raise ValueError("own_batches needs a batch_size: the full-data row list is the same for every sample")
-    if not isinstance(handle, CustomTarget):
-        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
-    n, d = x.shape
-    _req(x, (n, d), name="x")
-    if len(data.shape) != 2:
-        raise ValueError(f"data: expected a two-dimensional array, got {data.shape}")
-    t, c = data.shape
-    _req(data, (t, c), name="data")
-    if params is not None:
-        if len(params.shape) != 1:
-            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
-        _req(params, params.shape, name="params")
-    lp = ctx.empty((n,))
-    grad = ctx.empty((n, d)) if want_grad else None
-    if n > 0 and own_batches:
-        ctx.check(ctx.lib.gmmvi_target_custom_data_tape_own_batches(
-            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c, int(batch_size),
-            int(seed) & 0xFFFFFFFFFFFFFFFF, int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks),
-            int(tape_capacity), int(scratch_bytes)))
-    elif n > 0:
-        ctx.check(ctx.lib.gmmvi_target_custom_data_tape(
-            ctx.handle, handle.handle, d, None if params is None else params.ptr, data.ptr, t, c,
-            0 if batch_size is None else 1, t if batch_size is None else int(batch_size), int(seed) & 0xFFFFFFFFFFFFFFFF,
-            int(call) & 0xFFFFFFFF, x.ptr, n, lp.ptr, None if grad is None else grad.ptr, int(chunks), int(tape_capacity),
-            int(scratch_bytes)))
-    return lp, grad
+    return _target_custom_data(ctx, "gmmvi_target_custom_data_tape", handle, params, data, x, want_grad, batch_size, seed, call,
+                               chunks, own_batches, int(tape_capacity), int(scratch_bytes))
 
 
 def custom_data_predictive(ctx, handle, params, rows, x, chunks=0):
@@ -352,25 +323,10 @@ def custom_data_predictive(ctx, handle, params, rows, x, chunks=0):
     sample x[n] on rows[m], per row  lpd = log mean_n exp(l),  mean = mean_n l  and  var = the unbiased variance of l over the
     samples.  rows [M, C]: the evaluation set; chunks: 0 lets the library plan the launch, a positive number forces that many
     row chunks (no output bit depends on it).  -> (lpd [M], mean [M], var [M])."""
-    if not isinstance(handle, CustomTarget):
-        raise TypeError(f"handle: expected CustomTarget, got {type(handle)}")
-    if len(x.shape) != 2:
-        raise ValueError(f"x: expected a two-dimensional array, got {x.shape}")
-    n, d = x.shape
-    _req(x, (n, d), name="x")
-    if len(rows.shape) != 2:
-        raise ValueError(f"rows: expected a two-dimensional array, got {rows.shape}")
-    m, c = rows.shape
-    _req(rows, (m, c), name="rows")
-    if n < 1 or m < 1:
-        raise ValueError(f"the predictive density needs at least one sample and one row, got {n} and {m}")
-    if params is not None:
-        if len(params.shape) != 1:
-            raise ValueError(f"params: expected a one-dimensional array, got {params.shape}")
-        _req(params, params.shape, name="params")
+    n, d, m, c = _custom_arguments(handle, x, params, rows, predictive=True)
     lpd, mean, var = ctx.empty((m,)), ctx.empty((m,)), ctx.empty((m,))
-    ctx.check(ctx.lib.gmmvi_custom_data_predictive(ctx.handle, handle.handle, d, None if params is None else params.ptr, rows.ptr, m,
-                                                   c, x.ptr, n, lpd.ptr, mean.ptr, var.ptr, int(chunks)))
+    ctx.check(ctx.lib.gmmvi_custom_data_predictive(ctx.handle, handle.handle, d, _ptr(params), rows.ptr, m, c, x.ptr, n, lpd.ptr,
+                                                   mean.ptr, var.ptr, int(chunks)))
     return lpd, mean, var
 
 
