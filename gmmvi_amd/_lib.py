@@ -192,6 +192,7 @@ _PROTOS = {
     "gmmvi_custom_target_compile_autodiff": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_autodiff_probe": (_i, [_i, _f, _f, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
     "gmmvi_autodiff_probe_special": (_i, [_i, _f, _f, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
+    "gmmvi_autodiff_probe_extra": (_i, [_i, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
     "gmmvi_custom_target_check_data": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i)]),
@@ -204,6 +205,7 @@ _PROTOS = {
     "gmmvi_target_custom_tape": (_i, [_p, _p, _i, _p, _p, _i, _p, _p, _i, _sz]),
     "gmmvi_tape_probe": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gmmvi_tape_probe_special": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
+    "gmmvi_tape_probe_extra": (_i, [_i, _f, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gmmvi_custom_target_check_data_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -286,6 +288,10 @@ AUTODIFF_OPS = _autodiff_ops()
 # constant: no tangent, no record).
 SPECIAL_OPS = ("lgamma", "erf", "erff", "erfc", "erfcf", "digamma", "sigmoid", "softplus", "log_sigmoid",
                "logaddexp", "logaddexp_tf", "logaddexp_ft", "trigamma")
+
+# The operations of gmmvi_autodiff_probe_extra and gmmvi_tape_probe_extra in index order: the one-operand functions that came
+# after SPECIAL_OPS, which stays as it is.  gmmvi_erfcx, gmmvi_ndtr and gmmvi_log_ndtr go by their names without ``gmmvi_``.
+EXTRA_OPS = ("erfcx", "ndtr", "log_ndtr", "sinh", "sinhf", "cosh", "coshf", "asin", "asinf", "acos", "acosf")
 
 
 def load():

@@ -1,5 +1,6 @@
 // gmmvi_autodiff_probe (include/gmmvi_hip.h): one operation of the dual-number text of differentiated user-defined targets,
-// evaluated on the host; gmmvi_autodiff_probe_special: the same for its special functions, a list of their own.  The text is
+// evaluated on the host; gmmvi_autodiff_probe_special and gmmvi_autodiff_probe_extra: the same for its special functions, two
+// lists of their own (the second one the normal distribution's functions and sinh, cosh, asin, acos).  The text is
 // the one the run-time compiler gets (custom_target_special.inc and custom_target_autodiff.inc, their raw-string delimiters
 // taken off by the Makefile), without the adapter, which needs a user's function.  Host code only.
 #include "common.h"
@@ -80,6 +81,26 @@ extern "C" int gmmvi_autodiff_probe_special(int op, float a, float da, float b, 
         case __COUNTER__ - kBase: r = Dual(gmmvi_trigamma(a)); break;      // a float function only: a constant
         default:
             return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_special: unknown operation " + std::to_string(op));
+    }
+    *value = r.v;
+    *tangent = r.d[0];
+    return GMMVI_OK;
+}
+
+// the normal distribution's functions and the four elementary ones that came with them, in the order of _lib.EXTRA_OPS
+extern "C" int gmmvi_autodiff_probe_extra(int op, float a, float da, float* value, float* tangent) {
+    if (!value || !tangent)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_extra: value and tangent must not be NULL");
+    constexpr int kBase = __COUNTER__ + 1;
+    Dual A(a), r;
+    A.d[0] = da;
+    switch (op) {
+        case __COUNTER__ - kBase: r = gmmvi_erfcx(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_ndtr(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_log_ndtr(A); break;
+        PROBE_UNARY(sinh) PROBE_UNARY(cosh) PROBE_UNARY(asin) PROBE_UNARY(acos)
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_extra: unknown operation " + std::to_string(op));
     }
     *value = r.v;
     *tangent = r.d[0];

@@ -29,13 +29,14 @@ static const char* const kDataTapeText =
     ;
 static const char* const kLine = "\n";
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
-// the float instantiation of the user's template finds gmmvi_value and the six functions of custom_target_special.inc only if
-// they are declared before the template.  The hand-written mode gets the same line: its float code calls the six too.
+// the float instantiation of the user's template finds gmmvi_value and the nine functions of custom_target_special.inc only if
+// they are declared before the template.  The hand-written mode gets the same line: its float code calls the nine too.
 static const char* const kAutodiffPrelude =
     "__host__ __device__ inline float gmmvi_value(float); __host__ __device__ inline float gmmvi_digamma(float); "
     "__host__ __device__ inline float gmmvi_trigamma(float); __host__ __device__ inline float gmmvi_sigmoid(float); "
     "__host__ __device__ inline float gmmvi_softplus(float); __host__ __device__ inline float gmmvi_log_sigmoid(float); "
-    "__host__ __device__ inline float gmmvi_logaddexp(float, float); ";
+    "__host__ __device__ inline float gmmvi_logaddexp(float, float); __host__ __device__ inline float gmmvi_erfcx(float); "
+    "__host__ __device__ inline float gmmvi_ndtr(float); __host__ __device__ inline float gmmvi_log_ndtr(float); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
 

@@ -9,7 +9,8 @@ R"GMMVI_AD(
 // Tie rules: fabs has tangent 0 at +-0; fmax and fmin take the first operand's tangent on a tie; comparisons look at the values
 // only, so a branch on a comparison differentiates the branch taken.  sqrt and rsqrt at 0 and log at 0 have infinite
 // derivatives, as in IEEE arithmetic.  lgamma has a NaN tangent at a <= 0; gmmvi_logaddexp has the tangents 1/2 and 1/2 on a tie;
-// gmmvi_sigmoid is exactly 1 or 0 with tangent 0 beyond the range of expf.  There is no conversion from a dual to float:
+// gmmvi_sigmoid is exactly 1 or 0 with tangent 0 beyond the range of expf; asin and acos have infinite tangents at |a| = 1;
+// gmmvi_erfcx has the tangent -inf, not NaN, where its value has overflowed.  There is no conversion from a dual to float:
 // gmmvi_value(t) is the only way down.
 
 namespace gmmvi_ad {
@@ -153,8 +154,17 @@ GMMVI_AD_ALIAS2(fmax) GMMVI_AD_ALIAS2(fmin) GMMVI_AD_ALIAS2(pow)
 GMMVI_AD_FN Dual lgamma(const Dual& a) { return chain(::lgammaf(a.v), ::gmmvi_digamma(a.v), a); }
 GMMVI_AD_FN Dual erf(const Dual& a) { return chain(::erff(a.v), gmmvi_special::erf_partial(a.v), a); }
 GMMVI_AD_FN Dual erfc(const Dual& a) { return chain(::erfcf(a.v), -gmmvi_special::erf_partial(a.v), a); }
-GMMVI_AD_ALIAS1(erf) GMMVI_AD_ALIAS1(erfc)
+GMMVI_AD_FN Dual sinh(const Dual& a) { return chain(::sinhf(a.v), ::coshf(a.v), a); }
+GMMVI_AD_FN Dual cosh(const Dual& a) { return chain(::coshf(a.v), ::sinhf(a.v), a); }
+// tangents +-da / sqrt(1 - a^2): infinite at |a| = 1, NaN beyond
+GMMVI_AD_FN Dual asin(const Dual& a) { return chain(::asinf(a.v), gmmvi_special::asin_partial(a.v), a); }
+GMMVI_AD_FN Dual acos(const Dual& a) { return chain(::acosf(a.v), -gmmvi_special::asin_partial(a.v), a); }
+GMMVI_AD_ALIAS1(erf) GMMVI_AD_ALIAS1(erfc) GMMVI_AD_ALIAS1(sinh) GMMVI_AD_ALIAS1(cosh) GMMVI_AD_ALIAS1(asin) GMMVI_AD_ALIAS1(acos)
 #undef GMMVI_AD_ALIAS1
+// gmmvi_erfcx has the tangent -inf where its value has overflowed; gmmvi_log_ndtr a finite one for every finite a
+GMMVI_AD_FN Dual gmmvi_erfcx(const Dual& a) { return chain(::gmmvi_erfcx(a.v), gmmvi_special::erfcx_partial(a.v), a); }
+GMMVI_AD_FN Dual gmmvi_ndtr(const Dual& a) { return chain(::gmmvi_ndtr(a.v), gmmvi_special::ndtr_partial(a.v), a); }
+GMMVI_AD_FN Dual gmmvi_log_ndtr(const Dual& a) { return chain(::gmmvi_log_ndtr(a.v), gmmvi_special::log_ndtr_partial(a.v), a); }
 GMMVI_AD_FN Dual gmmvi_digamma(const Dual& a) { return chain(::gmmvi_digamma(a.v), ::gmmvi_trigamma(a.v), a); }
 // s sigmoid(-a), not s (1 - s), which cancels for large a
 GMMVI_AD_FN Dual gmmvi_sigmoid(const Dual& a) { const float s = ::gmmvi_sigmoid(a.v); return chain(s, s * ::gmmvi_sigmoid(-a.v), a); }

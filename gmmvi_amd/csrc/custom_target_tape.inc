@@ -189,8 +189,16 @@ GMMVI_TAPE_ALIAS2(fmax) GMMVI_TAPE_ALIAS2(fmin) GMMVI_TAPE_ALIAS2(pow)
 GMMVI_TAPE_FN Var lgamma(const Var& a) { return node(::lgammaf(a.v), a, ::gmmvi_digamma(a.v)); }
 GMMVI_TAPE_FN Var erf(const Var& a) { return node(::erff(a.v), a, gmmvi_special::erf_partial(a.v)); }
 GMMVI_TAPE_FN Var erfc(const Var& a) { return node(::erfcf(a.v), a, -gmmvi_special::erf_partial(a.v)); }
-GMMVI_TAPE_ALIAS1(erf) GMMVI_TAPE_ALIAS1(erfc)
+GMMVI_TAPE_FN Var sinh(const Var& a) { return node(::sinhf(a.v), a, ::coshf(a.v)); }
+GMMVI_TAPE_FN Var cosh(const Var& a) { return node(::coshf(a.v), a, ::sinhf(a.v)); }
+GMMVI_TAPE_FN Var asin(const Var& a) { return node(::asinf(a.v), a, gmmvi_special::asin_partial(a.v)); }
+GMMVI_TAPE_FN Var acos(const Var& a) { return node(::acosf(a.v), a, -gmmvi_special::asin_partial(a.v)); }
+GMMVI_TAPE_ALIAS1(erf) GMMVI_TAPE_ALIAS1(erfc) GMMVI_TAPE_ALIAS1(sinh) GMMVI_TAPE_ALIAS1(cosh) GMMVI_TAPE_ALIAS1(asin)
+GMMVI_TAPE_ALIAS1(acos)
 #undef GMMVI_TAPE_ALIAS1
+GMMVI_TAPE_FN Var gmmvi_erfcx(const Var& a) { return node(::gmmvi_erfcx(a.v), a, gmmvi_special::erfcx_partial(a.v)); }
+GMMVI_TAPE_FN Var gmmvi_ndtr(const Var& a) { return node(::gmmvi_ndtr(a.v), a, gmmvi_special::ndtr_partial(a.v)); }
+GMMVI_TAPE_FN Var gmmvi_log_ndtr(const Var& a) { return node(::gmmvi_log_ndtr(a.v), a, gmmvi_special::log_ndtr_partial(a.v)); }
 GMMVI_TAPE_FN Var gmmvi_digamma(const Var& a) { return node(::gmmvi_digamma(a.v), a, ::gmmvi_trigamma(a.v)); }
 GMMVI_TAPE_FN Var gmmvi_sigmoid(const Var& a) { const float s = ::gmmvi_sigmoid(a.v); return node(s, a, s * ::gmmvi_sigmoid(-a.v)); }
 GMMVI_TAPE_FN Var gmmvi_softplus(const Var& a) { return node(::gmmvi_softplus(a.v), a, ::gmmvi_sigmoid(a.v)); }

@@ -1,7 +1,7 @@
 // gmmvi_tape_probe (include/gmmvi_hip.h): one operation of the tape's number type (custom_target_tape.inc, its raw-string
 // delimiters taken off by the Makefile, without the kernels, which need a user's function), run on a tape in host memory.  The
 // operations and their order are those of autodiff_probe.hip, gmmvi_tape_probe_special's those of
-// gmmvi_autodiff_probe_special.  Host code only.
+// gmmvi_autodiff_probe_special, gmmvi_tape_probe_extra's those of gmmvi_autodiff_probe_extra.  Host code only.
 #include "common.h"
 
 #define GMMVI_TAPE_NO_KERNELS
@@ -106,4 +106,28 @@ extern "C" int gmmvi_tape_probe_special(int op, float a, float b, int a_is_const
             return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_special: unknown operation " + std::to_string(op));
     }
     return report(r, rec, value, pa, pb, records);
+}
+
+// the operations of gmmvi_autodiff_probe_extra, in its order: one operand, node 0 or a constant
+extern "C" int gmmvi_tape_probe_extra(int op, float a, int a_is_const, float* value, float* pa, int* records) {
+    if (!value || !pa || !records)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_extra: value, pa and records must not be NULL");
+    constexpr int kBase = __COUNTER__ + 1;
+    constexpr int kCap = 4;
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, 2};   // stride 1, D = 2
+    gmmvi_tape::count() = 0;
+    const Var A = a_is_const ? Var(a) : Var(a, 0);
+    Var r;
+    switch (op) {
+        case __COUNTER__ - kBase: r = gmmvi_erfcx(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_ndtr(A); break;
+        case __COUNTER__ - kBase: r = gmmvi_log_ndtr(A); break;
+        PROBE_UNARY(sinh) PROBE_UNARY(cosh) PROBE_UNARY(asin) PROBE_UNARY(acos)
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_extra: unknown operation " + std::to_string(op));
+    }
+    float pb = 0.f;
+    return report(r, rec, value, pa, &pb, records);
 }

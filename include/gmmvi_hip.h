@@ -353,8 +353,11 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  *   - lgamma, and erf erfc, these two also under their f-suffixed names: the values are ROCm's lgammaf, erff and erfcf, the
  *     derivatives gmmvi_digamma(a) and +-2 / sqrt(pi) exp(-a^2).  lgammaf itself stays a float function: on a T it is a
  *     compile error, spell it lgamma;
+ *   - sinh cosh asin acos, each also under its f-suffixed name: the values are ROCm's, the derivatives cosh, sinh and
+ *     +-1 / sqrt(1 - a^2), which is infinite at |a| = 1 and NaN beyond;
  *   - gmmvi_digamma(t), gmmvi_sigmoid(t), gmmvi_softplus(t), gmmvi_log_sigmoid(t), and gmmvi_logaddexp between T and T, T and
  *     float, float and T (below);
+ *   - gmmvi_erfcx(t), gmmvi_ndtr(t), gmmvi_log_ndtr(t) (below);
  *   - gmmvi_value(t): the float value of a float and of a dual.
  * A float converts to a T (a constant: all tangents 0); a T does not convert to float, so a function outside this list, such
  * as tgammaf, erfinvf or lgammaf, on a T is a compile error (GMMVI_ERR_ARG with the compiler log, as for any source).
@@ -370,8 +373,18 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  *   - float gmmvi_softplus(float x): log(1 + e^x) = fmax(x, 0) + log1p(exp(-|x|));
  *   - float gmmvi_log_sigmoid(float x): -gmmvi_softplus(-x);
  *   - float gmmvi_logaddexp(float a, float b): log(e^a + e^b) = max + log1p(exp(-|a - b|)); a == b, equal infinities
- *     included, gives a + ln 2 and no NaN.
- * On a T: gmmvi_digamma has the derivative gmmvi_trigamma(a); gmmvi_sigmoid s * sigmoid(-a) (not s (1 - s), which cancels for
+ *     included, gives a + ln 2 and no NaN;
+ *   - float gmmvi_erfcx(float x): e^(x^2) erfc(x), from a polynomial of its own and expf, not from erfcf.  Finite and positive
+ *     for every finite x >= 0 (1 / (x sqrt(pi)) where x^2 overflows); +inf where 2 e^(x^2) overflows (x < -9.38); NaN for NaN;
+ *   - float gmmvi_ndtr(float x): the normal distribution function Phi(x) = erfc(-x / sqrt(2)) / 2, as erfcx(|x| / sqrt(2))
+ *     e^(-x^2 / 2) / 2 or one minus that: exactly 0 or 1 only where fp32 has nothing closer;
+ *   - float gmmvi_log_ndtr(float x): log Phi(x); for x < 0 log(erfcx(-x / sqrt(2)) / 2) - x^2 / 2, finite for every finite x whose
+ *     x^2 / 2 is finite and -inf beyond and at -inf; for x >= 0 log1p(-(1 - Phi(x))), exactly 0 at +inf; NaN for NaN.  It never
+ *     takes the logarithm of an underflowed erfcf: log(0.5f * erfcf(-x * 0.70710678f)) is -inf from x = -14.2 on.
+ * On a T: gmmvi_erfcx has the derivative 2 a erfcx(a) - 2 / sqrt(pi) (for a >= 0 from a polynomial of its own, the difference
+ * cancels; -inf, never NaN, where the value has overflowed); gmmvi_ndtr phi(a) = e^(-a^2 / 2) / sqrt(2 pi) with the rounding of
+ * a^2 carried along; gmmvi_log_ndtr phi(a) / Phi(a), for a < 0 as sqrt(2 / pi) / erfcx(-a / sqrt(2)): finite and positive for
+ * every finite a at which phi is not below fp32's range, 0 at +inf.  gmmvi_digamma has the derivative gmmvi_trigamma(a); gmmvi_sigmoid s * sigmoid(-a) (not s (1 - s), which cancels for
  * large a); gmmvi_softplus sigmoid(a); gmmvi_log_sigmoid sigmoid(-a); gmmvi_logaddexp sigmoid(a - b) and sigmoid(b - a).
  * Tie rules: fabs has tangent 0 at +-0; fmax and fmin take the first operand's tangent on a tie; a branch on a comparison
  * differentiates the branch taken.  pow(T, T) takes no part of ln(a) in a direction in which the exponent does not move;
@@ -398,6 +411,9 @@ int gmmvi_autodiff_probe(int op, float a, float da, float b, float db, float* va
  * erf and erfc, each under both spellings; gmmvi_digamma, gmmvi_sigmoid, gmmvi_softplus, gmmvi_log_sigmoid, gmmvi_logaddexp in its
  * three operand forms, and gmmvi_trigamma of the float a (a constant: tangent 0). */
 int gmmvi_autodiff_probe_special(int op, float a, float da, float b, float db, float* value, float* tangent);
+/* A second list, of one-operand functions (gmmvi_amd/_lib.py EXTRA_OPS names them in index order): gmmvi_erfcx, gmmvi_ndtr,
+ * gmmvi_log_ndtr; sinh, cosh, asin and acos, each under both spellings. */
+int gmmvi_autodiff_probe_extra(int op, float a, float da, float* value, float* tangent);
 
 /* ---- user-defined targets summed over a data set --------------------------------------------------------------------------------
  * Posteriors of the shape  log p(x) = log prior(x) + sum over the data rows r of log p(data_r | x):  the source defines one
@@ -545,6 +561,8 @@ int gmmvi_tape_probe(int op, float a, float b, int a_is_const, int b_is_const, f
 /* The same for the special functions: op indexes the operations in the order of gmmvi_autodiff_probe_special. */
 int gmmvi_tape_probe_special(int op, float a, float b, int a_is_const, int b_is_const, float* value, float* pa, float* pb,
                              int* records);
+/* The same for the one-operand functions of gmmvi_autodiff_probe_extra, in its order. */
+int gmmvi_tape_probe_extra(int op, float a, int a_is_const, float* value, float* pa, int* records);
 
 /* ---- targets summed over a data set, differentiated on a tape ------------------------------------------------------------------
  * The source of the data mode, unchanged (gmmvi_user_row and gmmvi_user_prior, templates over the number type; compiled with
