@@ -106,3 +106,24 @@ extern "C" int gmmvi_autodiff_probe_extra(int op, float a, float da, float* valu
     *tangent = r.d[0];
     return GMMVI_OK;
 }
+
+// one vector primitive on the inputs (custom_target_vector.inc and its Seed overloads), in the order of _lib.VECTOR_OPS, in the
+// pass seeded at `seed_first`: tangents[j] is the partial derivative by x[seed_first + j]
+extern "C" int gmmvi_autodiff_probe_vector(int op, const float* x, int D, int first, int n, const float* c, float center,
+                                           int seed_first, float* value, float* tangents) {
+    if (!x || !value || !tangents || D < 1 || first < 0 || seed_first < 0 || (n > 0 && (first > D - n || (op < 2 && !c))))
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_vector: needs x, value, tangents, D >= 1, seed_first >= 0, "
+                                                  "0 <= first, first + n <= D and, for n > 0 and the first two operations, c");
+    const gmmvi_ad::Seed seed{x, seed_first};
+    Dual r;
+    switch (op) {
+        case gmmvi_vector::DOT: r = gmmvi_dot(seed, first, c, n); break;
+        case gmmvi_vector::SQDIST: r = gmmvi_sqdist(seed, first, c, n); break;
+        case gmmvi_vector::SUMSQ: r = gmmvi_sumsq(seed, first, n, center); break;
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_vector: unknown operation " + std::to_string(op));
+    }
+    *value = r.v;
+    for (int j = 0; j < gmmvi_ad::W; ++j) tangents[j] = r.d[j];
+    return GMMVI_OK;
+}

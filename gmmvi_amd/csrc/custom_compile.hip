@@ -10,8 +10,9 @@
 static const char* const kWrapText =
 #include "custom_target_wrap.inc"
     ;
-static const char* const kSpecialText =
+static const char* const kSpecialText =                                   // the float functions: special, then the vector primitives
 #include "custom_target_special.inc"
+#include "custom_target_vector.inc"
     ;
 static const char* const kAutodiffText =
 #include "custom_target_autodiff.inc"
@@ -29,14 +30,18 @@ static const char* const kDataTapeText =
     ;
 static const char* const kLine = "\n";
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
-// the float instantiation of the user's template finds gmmvi_value and the nine functions of custom_target_special.inc only if
-// they are declared before the template.  The hand-written mode gets the same line: its float code calls the nine too.
+// the float instantiation of the user's template finds gmmvi_value, the nine functions of custom_target_special.inc and the three
+// of custom_target_vector.inc only if they are declared before the template.  The hand-written mode gets the same line: its float
+// code calls them too.
 static const char* const kAutodiffPrelude =
     "__host__ __device__ inline float gmmvi_value(float); __host__ __device__ inline float gmmvi_digamma(float); "
     "__host__ __device__ inline float gmmvi_trigamma(float); __host__ __device__ inline float gmmvi_sigmoid(float); "
     "__host__ __device__ inline float gmmvi_softplus(float); __host__ __device__ inline float gmmvi_log_sigmoid(float); "
     "__host__ __device__ inline float gmmvi_logaddexp(float, float); __host__ __device__ inline float gmmvi_erfcx(float); "
-    "__host__ __device__ inline float gmmvi_ndtr(float); __host__ __device__ inline float gmmvi_log_ndtr(float); ";
+    "__host__ __device__ inline float gmmvi_ndtr(float); __host__ __device__ inline float gmmvi_log_ndtr(float); "
+    "__host__ __device__ inline float gmmvi_dot(const float*, int, const float*, int); "
+    "__host__ __device__ inline float gmmvi_sqdist(const float*, int, const float*, int); "
+    "__host__ __device__ inline float gmmvi_sumsq(const float*, int, int, float); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
 

@@ -197,6 +197,24 @@ struct Seed {
     }
 };
 
+// ---- vector primitives on the inputs (custom_target_vector.inc has their values): tangent j is the partial derivative by
+// x[x.first + j] where that index lies in [first, first + n), else 0; no loop over n carries tangents ----------------------------
+GMMVI_AD_FN Dual gmmvi_dot(const Seed& x, int first, const float* c, int n) {
+    Dual r; r.v = ::gmmvi_vector::dot_value(x.x + first, c, n);
+    GMMVI_AD_EACH { const int k = x.first + j - first; r.d[j] = k >= 0 && k < n ? c[k] : 0.f; }
+    return r;
+}
+GMMVI_AD_FN Dual gmmvi_sqdist(const Seed& x, int first, const float* c, int n) {
+    Dual r; r.v = ::gmmvi_vector::sqdist_value(x.x + first, c, n);
+    GMMVI_AD_EACH { const int k = x.first + j - first; r.d[j] = k >= 0 && k < n ? 2.f * (x.x[first + k] - c[k]) : 0.f; }
+    return r;
+}
+GMMVI_AD_FN Dual gmmvi_sumsq(const Seed& x, int first, int n, float center) {
+    Dual r; r.v = ::gmmvi_vector::sumsq_value(x.x + first, n, center);
+    GMMVI_AD_EACH { const int k = x.first + j - first; r.d[j] = k >= 0 && k < n ? 2.f * (x.x[first + k] - center) : 0.f; }
+    return r;
+}
+
 }  // namespace gmmvi_ad
 
 // (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there)

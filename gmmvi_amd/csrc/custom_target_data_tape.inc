@@ -43,26 +43,7 @@ using gmmvi_tape::Var;
 
 #define GMMVI_DATA_TAPE_FN __host__ __device__ __forceinline__
 
-// Adds d out / d x[i] into acc[i * stride] for every input i.  rp / ap: the lane's record 0 and adjoint slot 0.
-GMMVI_DATA_TAPE_FN void sweep(const Var& out, int D, RecPtr rp, AdjPtr ap, size_t stride, float* acc) {
-    if (out.id < 0) return;                                          // a constant: nothing to add
-    if (out.id < D) { acc[(size_t)out.id * stride] += 1.f; return; } // an input
-    int r = out.id - D;
-    ap[(size_t)r * stride] = 1.f;
-    for (; r >= 0; --r) {
-        const Rec4 v = rp[(size_t)r * stride];
-        const float w = ap[(size_t)r * stride];
-        if (v.x >= 0) {
-            const float d = gmmvi_tape::bits_float(v.z) * w;
-            if (v.x < D) acc[(size_t)v.x * stride] += d; else ap[(size_t)(v.x - D) * stride] += d;
-        }
-        if (v.y >= 0) {
-            const float d = gmmvi_tape::bits_float(v.w) * w;
-            if (v.y < D) acc[(size_t)v.y * stride] += d; else ap[(size_t)(v.y - D) * stride] += d;
-        }
-    }
-}
-
+// The sweep is gmmvi_tape::sweep with the accumulator's stride: d out / d x[i] goes into acc[i * stride].
 // One lane's share of a chunk: positions begin .. end - 1 of the row list, row_at(p) the floats of the row at position p.
 // gmmvi_tape::tape() is set (stride, cap, D and the base the lane's rp / ap belong to).  -> the longest record count of a row.
 template <class RowAt>
@@ -77,7 +58,7 @@ GMMVI_DATA_TAPE_FN int rows_lane(const float* x, int D, const float* params, int
         value += out.v;
         const int made = gmmvi_tape::count();
         if (made > longest) longest = made;
-        if (longest <= cap) sweep(out, D, rp, ap, stride, acc);
+        if (longest <= cap) gmmvi_tape::sweep(out, D, rp, ap, stride, x, acc, stride);
     }
     ap[0] = value;                                                   // the tape is done with: slot 0 carries the chunk's value sum
     return longest;
@@ -100,7 +81,7 @@ GMMVI_DATA_TAPE_FN int finish_lane(const float* x, int D, const float* params, i
     *lp = scaled + prior.v;
     const int made = gmmvi_tape::count();
     if (made > cap) return made;
-    sweep(prior, D, rp, ap, stride, acc);
+    gmmvi_tape::sweep(prior, D, rp, ap, stride, x, acc, stride);
     for (int i = 0; i < D; ++i) grad[i] = acc[(size_t)i * stride];
     return made;
 }

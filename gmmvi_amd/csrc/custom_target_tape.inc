@@ -8,7 +8,9 @@ R"GMMVI_TAPE(
 //
 // Node ids: id < 0 a constant; 0 <= id < D the input x[id]; id >= D record id - D.  A record is {ia, ib, pa, pb}: the ids of
 // the parents and the partial derivatives of the node by them (ib = -1: one parent; a constant parent keeps its negative id
-// and takes no part in the sweep).  Record r of lane l lies at rec[r * stride + l], its adjoint at adj[r * stride + l]: on the
+// and takes no part in the sweep).  ia <= -2 marks a vector record, the one node of a gmmvi_dot, gmmvi_sqdist or gmmvi_sumsq
+// call on the inputs (custom_target_vector.inc): ia = -2 - (4 n + kind), ib = first, and {pa, pb} hold the 64-bit address of
+// c, or the bits of center in pa.  Record r of lane l lies at rec[r * stride + l], its adjoint at adj[r * stride + l]: on the
 // device stride = 64, a wave's record r is 1 KiB of consecutive memory and every access below is an ordinary per-lane vector
 // load or store; on the host (csrc/tape_probe.hip) stride = 1 and l = 0.
 // The partial derivatives and the tie rules are those of the forward mode (custom_target_autodiff.inc): fabs has partial 0 at
@@ -55,21 +57,22 @@ GMMVI_TAPE_FN float rsqrt_value(float a) { return 1.f / ::sqrtf(a); }
 GMMVI_TAPE_FN int float_bits(float f) { union { float f; int i; } u; u.f = f; return u.i; }
 GMMVI_TAPE_FN float bits_float(int i) { union { float f; int i; } u; u.i = i; return u.f; }
 
-// Appends {ia, ib, pa, pb} and zeroes the record's adjoint; -> the id of the new node.  Beyond the capacity nothing is stored,
+// Appends {ia, ib, z, w} and zeroes the record's adjoint; -> the id of the new node.  Beyond the capacity nothing is stored,
 // the count still advances: the values stay right and the lane knows how long its tape would have been.
-GMMVI_TAPE_FN int push(int ia, int ib, float pa, float pb) {
+GMMVI_TAPE_FN int push_bits(int ia, int ib, int z, int w) {
     const Tape& t = tape();
     int& c = count();
     const int r = c;
     if (r < t.cap) {
         const size_t at = (size_t)r * (size_t)t.stride + (size_t)lane();
-        Rec4 v; v.x = ia; v.y = ib; v.z = float_bits(pa); v.w = float_bits(pb);
+        Rec4 v; v.x = ia; v.y = ib; v.z = z; v.w = w;
         t.rec[at] = v;                                                  // one 16-byte store
         t.adj[at] = 0.f;
     }
     c = r + 1;
     return t.D + r;
 }
+GMMVI_TAPE_FN int push(int ia, int ib, float pa, float pb) { return push_bits(ia, ib, float_bits(pa), float_bits(pb)); }
 
 struct Var {
     float v;
@@ -222,6 +225,77 @@ struct Input {
     GMMVI_TAPE_FN Var operator[](int i) const { return Var(x[i], i); }
 };
 
+// ---- vector primitives on the inputs (custom_target_vector.inc has their values): one record per call whatever n is, none for
+// n <= 0.  The record keeps the address of c, not its contents: the sweep reads c[0 .. n) and the lane's x after the user's
+// function has returned ---------------------------------------------------------------------------------------------------------
+GMMVI_TAPE_FN int push_vector(int kind, int first, int n, int z, int w) { return push_bits(-2 - (4 * n + kind), first, z, w); }
+GMMVI_TAPE_FN int push_vector(int kind, int first, int n, const float* c) {
+    union { const float* p; int i[2]; } u; u.p = c;
+    return push_vector(kind, first, n, u.i[0], u.i[1]);
+}
+GMMVI_TAPE_FN Var gmmvi_dot(const Input& x, int first, const float* c, int n) {
+    if (n <= 0) return Var(0.f);
+    return Var(::gmmvi_vector::dot_value(x.x + first, c, n), push_vector(::gmmvi_vector::DOT, first, n, c));
+}
+GMMVI_TAPE_FN Var gmmvi_sqdist(const Input& x, int first, const float* c, int n) {
+    if (n <= 0) return Var(0.f);
+    return Var(::gmmvi_vector::sqdist_value(x.x + first, c, n), push_vector(::gmmvi_vector::SQDIST, first, n, c));
+}
+GMMVI_TAPE_FN Var gmmvi_sumsq(const Input& x, int first, int n, float center) {
+    if (n <= 0) return Var(0.f);
+    return Var(::gmmvi_vector::sumsq_value(x.x + first, n, center), push_vector(::gmmvi_vector::SUMSQ, first, n, float_bits(center), 0));
+}
+
+// The vector record v with adjoint w: adds w * d node / d x[first + i] into g[(first + i) * g_stride], i ascending.  x: the lane's inputs.
+GMMVI_TAPE_FN void sweep_vector(const Rec4& v, float w, const float* x, float* g, size_t g_stride) {
+    const int code = -2 - v.x, kind = code & 3, n = code >> 2;
+    x += v.y;
+    g += (size_t)v.y * g_stride;
+    if (kind == ::gmmvi_vector::SUMSQ) {
+        const float center = bits_float(v.z);
+        for (int i = 0; i < n; ++i) g[(size_t)i * g_stride] += 2.f * (x[i] - center) * w;
+        return;
+    }
+    union { const float* p; int i[2]; } u; u.i[0] = v.z; u.i[1] = v.w;
+    const float* c = u.p;
+    if (kind == ::gmmvi_vector::DOT) {
+        for (int i = 0; i < n; ++i) g[(size_t)i * g_stride] += c[i] * w;
+    } else {
+        for (int i = 0; i < n; ++i) g[(size_t)i * g_stride] += 2.f * (x[i] - c[i]) * w;
+    }
+}
+
+// The sweep of one lane: adds d out / d x[i] into g[i * g_stride] for every input i, walking the records from the output's own back
+// to record 0 (records made after the output node are never visited).  rp / ap: the lane's record 0 and adjoint slot 0, `stride`
+// floats / records from one record to the next.  A lane takes the branch of its own record's kind, whatever its neighbours hold.
+GMMVI_TAPE_FN void sweep(const Var& out, int D, RecPtr rp, AdjPtr ap, size_t stride, const float* x, float* g, size_t g_stride) {
+    if (out.id < 0) return;                                           // a constant: nothing to add
+    if (out.id < D) { g[(size_t)out.id * g_stride] += 1.f; return; }  // an input
+    int r = out.id - D;
+    ap[(size_t)r * stride] = 1.f;
+    while (r >= 0) {
+        // the loop of the scalar records, which a vector record leaves: its code stands outside this loop
+        Rec4 v;
+        float w;
+        for (;;) {
+            v = rp[(size_t)r * stride];
+            w = ap[(size_t)r * stride];
+            if (v.x < -1) break;
+            if (v.x >= 0) {
+                const float d = bits_float(v.z) * w;
+                if (v.x < D) g[(size_t)v.x * g_stride] += d; else ap[(size_t)(v.x - D) * stride] += d;
+            }
+            if (v.y >= 0) {
+                const float d = bits_float(v.w) * w;
+                if (v.y < D) g[(size_t)v.y * g_stride] += d; else ap[(size_t)(v.y - D) * stride] += d;
+            }
+            if (--r < 0) return;
+        }
+        sweep_vector(v, w, x, g, g_stride);
+        --r;
+    }
+}
+
 }  // namespace gmmvi_tape
 
 // (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there;
@@ -265,24 +339,7 @@ extern "C" __global__ __launch_bounds__(64) void gmmvi_tape_grad(int D, const fl
     if (made > cap) return;
     float* g = grad + n * (size_t)D;
     for (int i = 0; i < D; ++i) g[i] = 0.f;
-    if (out.id < 0) return;                                  // a constant: the gradient is zero
-    if (out.id < D) { g[out.id] = 1.f; return; }             // an input
-    const RecPtr rp = (RecPtr)rec + wave_at + l;
-    const AdjPtr ap = (AdjPtr)adj + wave_at + l;
-    int r = out.id - D;
-    ap[(size_t)r * 64] = 1.f;
-    for (; r >= 0; --r) {
-        const Rec4 v = rp[(size_t)r * 64];
-        const float w = ap[(size_t)r * 64];
-        if (v.x >= 0) {
-            const float d = bits_float(v.z) * w;
-            if (v.x < D) g[v.x] += d; else ap[(size_t)(v.x - D) * 64] += d;
-        }
-        if (v.y >= 0) {
-            const float d = bits_float(v.w) * w;
-            if (v.y < D) g[v.y] += d; else ap[(size_t)(v.y - D) * 64] += d;
-        }
-    }
+    sweep(out, D, (RecPtr)rec + wave_at + l, (AdjPtr)adj + wave_at + l, 64, X + n * (size_t)D, g, 1);
 }
 #endif
 #undef GMMVI_TAPE_FN

@@ -131,3 +131,31 @@ extern "C" int gmmvi_tape_probe_extra(int op, float a, int a_is_const, float* va
     float pb = 0.f;
     return report(r, rec, value, pa, &pb, records);
 }
+
+// one vector primitive on the inputs (custom_target_vector.inc and its Input overloads), in the order of _lib.VECTOR_OPS: the
+// value, the record count, and the gradient [D] that gmmvi_tape::sweep, the sweep of both tape modes, leaves at stride 1
+extern "C" int gmmvi_tape_probe_vector(int op, const float* x, int D, int first, int n, const float* c, float center, float* value,
+                                       float* grad, int* records) {
+    if (!x || !value || !grad || !records || D < 1 || first < 0 || (n > 0 && (first > D - n || (op < 2 && !c))))
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_vector: needs x, value, grad, records, D >= 1, 0 <= first, "
+                                                  "first + n <= D and, for n > 0 and the first two operations, c");
+    constexpr int kCap = 4;
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, D};
+    gmmvi_tape::count() = 0;
+    const gmmvi_tape::Input in{x};
+    Var r;
+    switch (op) {
+        case gmmvi_vector::DOT: r = gmmvi_dot(in, first, c, n); break;
+        case gmmvi_vector::SQDIST: r = gmmvi_sqdist(in, first, c, n); break;
+        case gmmvi_vector::SUMSQ: r = gmmvi_sumsq(in, first, n, center); break;
+        default:
+            return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_vector: unknown operation " + std::to_string(op));
+    }
+    *value = r.v;
+    *records = gmmvi_tape::count();
+    for (int i = 0; i < D; ++i) grad[i] = 0.f;
+    gmmvi_tape::sweep(r, D, (gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, x, grad, 1);
+    return GMMVI_OK;
+}

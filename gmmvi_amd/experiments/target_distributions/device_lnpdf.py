@@ -30,6 +30,17 @@ call (csrc/custom_target_data.inc): log p(x) = log prior(x) + sum_r log p(data_r
 
 ``DeviceDataTapeLNPDF`` takes the same two templates and differentiates them in reverse mode, one row at a time on a short tape
 (csrc/custom_target_data_tape.inc): such posteriors up to the largest diagonal-covariance dimension.
+
+In every one of these texts ``x`` also takes three vector primitives, which each mode differentiates in closed form
+(csrc/custom_target_vector.inc; on the tape one record per call whatever ``n`` is, in forward mode no loop with tangents):
+
+    gmmvi_dot(x, first, c, n)          sum over i < n of c[i] * x[first + i]
+    gmmvi_sqdist(x, first, c, n)       sum over i < n of (x[first + i] - c[i])^2
+    gmmvi_sumsq(x, first, n, center)   sum over i < n of (x[first + i] - center)^2
+
+``c`` is a ``const float*`` that stays readable and unchanged until the kernel ends (``row``, ``params``, a static table; never an
+array local to the function), ``0 <= first`` and ``first + n <= D`` are the caller's duty, ``n <= 0`` gives the constant 0.  A
+logistic row is then ``T z = gmmvi_dot(x, 0, row, D) * row[D];`` and a normal prior ``-0.5f / (s * s) * gmmvi_sumsq(x, 0, D, m)``.
 """
 import numpy as np
 

@@ -391,6 +391,21 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  * sqrt, rsqrt and log at 0 have the infinite derivatives of IEEE arithmetic.  lgamma of a T has a NaN derivative at a <= 0
  * (digamma's; the value is still lgammaf's); gmmvi_logaddexp has the derivatives exactly 1/2 and 1/2 on a tie; gmmvi_sigmoid
  * beyond the range of expf is exactly 1 or 0 with derivative exactly 0.
+ * Vector primitives on the input view x (csrc/custom_target_vector.inc; declared and defined with the float functions above, in
+ * every mode).  X is whatever the mode passes as x: const float* on value calls and in the hand-written mode, the seeded view
+ * of this mode, the input view of the tape modes below; each returns that mode's number (float, dual, tape node):
+ *   - gmmvi_dot(X x, int first, const float* c, int n):         sum over i < n of c[i] * x[first + i];
+ *   - gmmvi_sqdist(X x, int first, const float* c, int n):      sum over i < n of (x[first + i] - c[i])^2;
+ *   - gmmvi_sumsq(X x, int first, int n, float center):         sum over i < n of (x[first + i] - center)^2.
+ * n <= 0 gives the constant 0: zero tangents, no record.  0 <= first and first + n <= D are the caller's duty, like the index of
+ * x[i]: the library cannot check them.  c must stay readable and unchanged until the kernel ends: it may point into row, params
+ * or a static table, not into an array local to the user's function, because the reverse sweep reads c after that function has
+ * returned; the rule holds in every mode, so that one text serves all of them.  The value comes from one function per primitive
+ * for all three number types, so a value call and a gradient call give the same bits.  Its order: four partial sums, element i
+ * into partial i mod 4 by one fused multiply-add (fmaf(c[i], x[i], s), fmaf(d, d, s) with d = x[first + i] - c[i] or - center),
+ * i ascending, then (s0 + s1) + (s2 + s3).  The derivatives are closed forms: c[k], 2 (x - c[k]), 2 (x - center) by
+ * x[first + k], nothing by c.  Forward mode: the tangents of a pass are 16 loads, there is no loop over n with tangents.  Tape
+ * modes: one record per call whatever n is (below).
  * The gradient takes ceil(D / W) passes of the dual instantiation, W = GMMVI_CUSTOM_AUTODIFF_TANGENTS, pass `first` writing
  * grad[first + j] for first + j < D; the value is that of the first pass.  That is ceil(D / W) * (1 + W) value evaluations per
  * sample, so a gradient call through such a handle is capped at GMMVI_CUSTOM_AUTODIFF_MAX_DIM; a value call is not. */
@@ -414,6 +429,12 @@ int gmmvi_autodiff_probe_special(int op, float a, float da, float b, float db, f
 /* A second list, of one-operand functions (gmmvi_amd/_lib.py EXTRA_OPS names them in index order): gmmvi_erfcx, gmmvi_ndtr,
  * gmmvi_log_ndtr; sinh, cosh, asin and acos, each under both spellings. */
 int gmmvi_autodiff_probe_extra(int op, float a, float da, float* value, float* tangent);
+/* One vector primitive on host arrays, in the pass seeded at seed_first (gmmvi_amd/_lib.py VECTOR_OPS names the operations in
+ * index order: gmmvi_dot, gmmvi_sqdist, gmmvi_sumsq): x[D], c[n] (unused by gmmvi_sumsq, as center is by the other two);
+ * *value and tangents[GMMVI_CUSTOM_AUTODIFF_TANGENTS], tangents[j] the derivative by x[seed_first + j].  An unknown op, a NULL
+ * array, D < 1, first < 0, seed_first < 0 or first + n > D: GMMVI_ERR_ARG. */
+int gmmvi_autodiff_probe_vector(int op, const float* x, int D, int first, int n, const float* c, float center, int seed_first,
+                                float* value, float* tangents);
 
 /* ---- user-defined targets summed over a data set --------------------------------------------------------------------------------
  * Posteriors of the shape  log p(x) = log prior(x) + sum over the data rows r of log p(data_r | x):  the source defines one
@@ -513,6 +534,12 @@ int gmmvi_target_custom_data_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_targ
  * have the same layout, 4 bytes per slot, and a record's adjoint is zeroed when the record is written.  Per lane and record that
  * is GMMVI_CUSTOM_TAPE_RECORD_BYTES of scratch.  The lane's record count is its own; all tape traffic is ordinary per-lane vector
  * loads and stores.
+ * A call of gmmvi_dot, gmmvi_sqdist or gmmvi_sumsq on the input view makes one record of another kind, whatever n is (none for
+ * n <= 0): ia = -2 - (4 n + kind), kind 0, 1, 2 in that order; ib = first; {pa, pb} hold the 64-bit address of c, or the bits of
+ * center in pa.  ia == -1 still means a constant parent, and the records of every other operation keep their bits.  The sweep
+ * that meets such a record with adjoint w adds c[i] w, 2 (x[first + i] - c[i]) w or 2 (x[first + i] - center) w to the adjoint of
+ * input first + i for i < n, i ascending; it reads c and the lane's x then, after the user's function has returned.  A lane
+ * sweeps the kind of its own record, whatever the other lanes of its wave hold at that record index.
  * Kernels: one lane is one sample, one wave per workgroup.  The lane records the user's function (every store guarded by the
  * capacity; beyond it the value stays right and the count keeps counting), then, in the same launch, seeds the output's adjoint
  * with 1 and walks its own records from the output back to the first.  Adjoints of inputs add up in the lane's own row of
@@ -563,6 +590,11 @@ int gmmvi_tape_probe_special(int op, float a, float b, int a_is_const, int b_is_
                              int* records);
 /* The same for the one-operand functions of gmmvi_autodiff_probe_extra, in its order. */
 int gmmvi_tape_probe_extra(int op, float a, int a_is_const, float* value, float* pa, int* records);
+/* One vector primitive on host arrays, op and the arrays as for gmmvi_autodiff_probe_vector: *value, *records (1, or 0 for
+ * n <= 0), and grad[D], what the sweep of the tape modes leaves from that one node with adjoint 1 (0 outside
+ * [first, first + n)).  An unknown op, a NULL array, D < 1, first < 0 or first + n > D: GMMVI_ERR_ARG. */
+int gmmvi_tape_probe_vector(int op, const float* x, int D, int first, int n, const float* c, float center, float* value, float* grad,
+                            int* records);
 
 /* ---- targets summed over a data set, differentiated on a tape ------------------------------------------------------------------
  * The source of the data mode, unchanged (gmmvi_user_row and gmmvi_user_prior, templates over the number type; compiled with
