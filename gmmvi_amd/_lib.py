@@ -194,6 +194,8 @@ _PROTOS = {
     "gmmvi_autodiff_probe_special": (_i, [_i, _f, _f, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
     "gmmvi_autodiff_probe_extra": (_i, [_i, _f, _f, C.POINTER(_f), C.POINTER(_f)]),
     "gmmvi_autodiff_probe_vector": (_i, [_i, _p, _i, _i, _i, _p, _f, _i, C.POINTER(_f), _p]),
+    "gmmvi_autodiff_probe_nodes": (_i, [_i, _p, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
+    "gmmvi_autodiff_probe_nodes_inputs": (_i, [_i, _p, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
     "gmmvi_custom_target_check_data": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i)]),
@@ -208,6 +210,8 @@ _PROTOS = {
     "gmmvi_tape_probe_special": (_i, [_i, _f, _f, _i, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gmmvi_tape_probe_extra": (_i, [_i, _f, _i, C.POINTER(_f), C.POINTER(_f), C.POINTER(_i)]),
     "gmmvi_tape_probe_vector": (_i, [_i, _p, _i, _i, _i, _p, _f, C.POINTER(_f), _p, C.POINTER(_i)]),
+    "gmmvi_tape_probe_nodes": (_i, [_i, _p, _i, _i, _i, _i, _i, C.POINTER(_f), _p, C.POINTER(_i)]),
+    "gmmvi_tape_probe_nodes_inputs": (_i, [_i, _p, _i, _i, _i, _i, C.POINTER(_f), _p, C.POINTER(_i)]),
     "gmmvi_custom_target_check_data_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
@@ -298,6 +302,9 @@ EXTRA_OPS = ("erfcx", "ndtr", "log_ndtr", "sinh", "sinhf", "cosh", "coshf", "asi
 # The operations of gmmvi_autodiff_probe_vector and gmmvi_tape_probe_vector in index order: the vector primitives on the input
 # view (csrc/custom_target_vector.inc), by their names without ``gmmvi_``.  The index is also the kind of the tape's vector record.
 VECTOR_OPS = ("dot", "sqdist", "sumsq")
+# The operations of gmmvi_autodiff_probe_nodes and gmmvi_tape_probe_nodes in index order: the primitives on arrays of the mode's
+# number type (gmmvi_wdot, gmmvi_logsumexp).  The index is also what the header of the tape's node-array record carries.
+NODE_OPS = ("wdot", "logsumexp")
 
 
 def load():

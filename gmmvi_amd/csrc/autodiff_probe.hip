@@ -127,3 +127,43 @@ extern "C" int gmmvi_autodiff_probe_vector(int op, const float* x, int D, int fi
     for (int j = 0; j < gmmvi_ad::W; ++j) tangents[j] = r.d[j];
     return GMMVI_OK;
 }
+
+// one primitive on an array of duals (gmmvi_wdot, gmmvi_logsumexp), in the order of _lib.NODE_OPS, in the pass seeded at
+// `seed_first`: the array is h[i] = tanh(x[src + i]), i < n, with every `every`-th entry (i % every == every - 1) the constant
+// tanhf(x[src + i]) instead; tangents[j] is the derivative by x[seed_first + j]
+extern "C" int gmmvi_autodiff_probe_nodes(int op, const float* x, int D, int first, int n, int src, int every, int seed_first,
+                                          float* value, float* tangents) {
+    constexpr int kMax = 64;
+    if (!x || !value || !tangents || op < 0 || op > gmmvi_vector::LOGSUMEXP || D < 1 || first < 0 || n < 0 || src < 0 || every < 0 ||
+        seed_first < 0 || n > kMax || src > D - n || first > D - n)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_nodes: needs a known operation, x, value, tangents, D >= 1, "
+                                                  "0 <= n <= 64, 0 <= first, 0 <= src, 0 <= every, 0 <= seed_first, "
+                                                  "first + n <= D and src + n <= D");
+    const gmmvi_ad::Seed seed{x, seed_first};
+    Dual h[kMax];
+    for (int i = 0; i < n; ++i)
+        h[i] = every > 0 && i % every == every - 1 ? Dual(::tanhf(x[src + i])) : tanh(seed[src + i]);
+    const Dual r = op == gmmvi_vector::WDOT ? gmmvi_wdot(seed, first, h, n) : gmmvi_logsumexp(h, n);
+    *value = r.v;
+    for (int j = 0; j < gmmvi_ad::W; ++j) tangents[j] = r.d[j];
+    return GMMVI_OK;
+}
+
+// the same call on an array whose entries are the inputs themselves, h[i] = x[src + i]: the tangents of gmmvi_logsumexp are then
+// its partials p_i bit for bit, and x may hold -inf (an array of -inf is the constant -inf)
+extern "C" int gmmvi_autodiff_probe_nodes_inputs(int op, const float* x, int D, int first, int n, int src, int seed_first,
+                                                 float* value, float* tangents) {
+    constexpr int kMax = 64;
+    if (!x || !value || !tangents || op < 0 || op > gmmvi_vector::LOGSUMEXP || D < 1 || first < 0 || n < 0 || src < 0 ||
+        seed_first < 0 || n > kMax || src > D - n || first > D - n)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_nodes_inputs: needs a known operation, x, value, tangents, "
+                                                  "D >= 1, 0 <= n <= 64, 0 <= first, 0 <= src, 0 <= seed_first, first + n <= D and "
+                                                  "src + n <= D");
+    const gmmvi_ad::Seed seed{x, seed_first};
+    Dual h[kMax];
+    for (int i = 0; i < n; ++i) h[i] = seed[src + i];
+    const Dual r = op == gmmvi_vector::WDOT ? gmmvi_wdot(seed, first, h, n) : gmmvi_logsumexp(h, n);
+    *value = r.v;
+    for (int j = 0; j < gmmvi_ad::W; ++j) tangents[j] = r.d[j];
+    return GMMVI_OK;
+}

@@ -215,6 +215,35 @@ GMMVI_AD_FN Dual gmmvi_sumsq(const Seed& x, int first, int n, float center) {
     return r;
 }
 
+// ---- primitives on arrays of duals (custom_target_vector.inc has their values, from the same two templates as the float
+// overloads; the user's call finds these by argument-dependent lookup on the element type).  One pass over n per call: entry i
+// adds its share to all W tangents at once, by fmaf, i ascending -----------------------------------------------------------------
+struct ValueAt {
+    const Dual* p;
+    GMMVI_AD_FN float operator()(int i) const { return p[i].v; }
+};
+// tangent j: sum over i of x[first + i] * h[i].d[j], and h[k].v where x[x.first + j] is x[first + k]
+GMMVI_AD_FN Dual gmmvi_wdot(const Seed& x, int first, const Dual* h, int n) {
+    Dual r(::gmmvi_vector::wdot_value(x.x + first, ValueAt{h}, n));
+    for (int i = 0; i < n; ++i) {
+        const float xi = x.x[first + i];
+        GMMVI_AD_EACH r.d[j] = ::fmaf(xi, h[i].d[j], r.d[j]);
+    }
+    GMMVI_AD_EACH { const int k = x.first + j - first; if (k >= 0 && k < n) r.d[j] += h[k].v; }
+    return r;
+}
+// tangent j: sum over i of p_i * a[i].d[j]; the constant -inf where the maximum is -inf
+GMMVI_AD_FN Dual gmmvi_logsumexp(const Dual* a, int n) {
+    float m, s;
+    Dual r(::gmmvi_vector::logsumexp_value(ValueAt{a}, n, m, s));
+    if (m == -__builtin_inff()) return r;
+    for (int i = 0; i < n; ++i) {
+        const float p = ::gmmvi_vector::logsumexp_partial(a[i].v, m, s);
+        GMMVI_AD_EACH r.d[j] = ::fmaf(p, a[i].d[j], r.d[j]);
+    }
+    return r;
+}
+
 }  // namespace gmmvi_ad
 
 // (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there)

@@ -10,9 +10,10 @@ R"GMMVI_TAPE(
 // the parents and the partial derivatives of the node by them (ib = -1: one parent; a constant parent keeps its negative id
 // and takes no part in the sweep).  ia <= -2 marks a vector record, the one node of a gmmvi_dot, gmmvi_sqdist or gmmvi_sumsq
 // call on the inputs (custom_target_vector.inc): ia = -2 - (4 n + kind), ib = first, and {pa, pb} hold the 64-bit address of
-// c, or the bits of center in pa.  Record r of lane l lies at rec[r * stride + l], its adjoint at adj[r * stride + l]: on the
-// device stride = 64, a wave's record r is 1 KiB of consecutive memory and every access below is an ordinary per-lane vector
-// load or store; on the host (csrc/tape_probe.hip) stride = 1 and l = 0.
+// c, or the bits of center in pa.  Kind 3 is the node-array record of gmmvi_wdot and gmmvi_logsumexp, a header behind
+// ceil(n / 2) payload slots ("primitives on arrays of nodes", below).  Record r of lane l lies at rec[r * stride + l], its
+// adjoint at adj[r * stride + l]: on the device stride = 64, a wave's record r is 1 KiB of consecutive memory and every access
+// below is an ordinary per-lane vector load or store; on the host (csrc/tape_probe.hip) stride = 1 and l = 0.
 // The partial derivatives and the tie rules are those of the forward mode (custom_target_autodiff.inc): fabs has partial 0 at
 // +-0; fmax and fmin give the first operand the partial 1 on a tie; comparisons look at the values only; pow with exponent 0
 // has partial 0 by the base; a constant exponent takes no part of ln(a).  An operation whose operands are all constants makes no
@@ -246,15 +247,78 @@ GMMVI_TAPE_FN Var gmmvi_sumsq(const Input& x, int first, int n, float center) {
     return Var(::gmmvi_vector::sumsq_value(x.x + first, n, center), push_vector(::gmmvi_vector::SUMSQ, first, n, float_bits(center), 0));
 }
 
-// The vector record v with adjoint w: adds w * d node / d x[first + i] into g[(first + i) * g_stride], i ascending.  x: the lane's inputs.
-GMMVI_TAPE_FN void sweep_vector(const Rec4& v, float w, const float* x, float* g, size_t g_stride) {
+// ---- primitives on arrays of nodes (custom_target_vector.inc has their values, from the same two templates as the float
+// overloads; the user's call finds these by argument-dependent lookup on the element type).  A call makes a node-array record,
+// kind 3 of the vector records, which spans 1 + ceil(n / 2) slots: the payload first, slot j = {id of entry 2 j, id of entry
+// 2 j + 1 or -1, 32 bits for each}, the bits h[i].v for gmmvi_wdot and the partial p_i for gmmvi_logsumexp; then the header
+// {-2 - (4 n + 3), first or -1, operation, 0}, behind its payload because the sweep walks backwards.  The result is the header's
+// node; no Var refers to a payload slot, whose zeroed adjoint is never read.  The record copies what the sweep needs: the array
+// may be local to the user's function.  Beyond the capacity nothing is stored and the count advances by slots, as for any record.
+// GMMVI_TAPE_NODES: csrc/custom_compile.hip defines it where the user's text names one of the two primitives.  Without it
+// neither the overloads nor the node-array branch of the sweep exist, so a kernel whose source does not call them is the kernel
+// it was before they came, and a text that reaches them under another spelling does not compile instead of making a record that
+// its sweep cannot read.
+#ifdef GMMVI_TAPE_NODES
+struct ValueAt {
+    const Var* p;
+    GMMVI_TAPE_FN float operator()(int i) const { return p[i].v; }
+};
+GMMVI_TAPE_FN Var gmmvi_wdot(const Input& x, int first, const Var* h, int n) {
+    if (n <= 0) return Var(0.f);
+    const float v = ::gmmvi_vector::wdot_value(x.x + first, ValueAt{h}, n);
+    for (int i = 0; i < n; i += 2) {
+        const bool two = i + 1 < n;
+        push_bits(h[i].id, two ? h[i + 1].id : -1, float_bits(h[i].v), two ? float_bits(h[i + 1].v) : 0);
+    }
+    return Var(v, push_vector(::gmmvi_vector::NODES, first, n, ::gmmvi_vector::WDOT, 0));
+}
+// the constant -inf where the maximum is -inf, and a constant where every entry is one
+GMMVI_TAPE_FN Var gmmvi_logsumexp(const Var* a, int n) {
+    float m, s;
+    const float v = ::gmmvi_vector::logsumexp_value(ValueAt{a}, n, m, s);
+    bool constant = true;
+    for (int i = 0; i < n; ++i) constant = constant && a[i].id < 0;
+    if (constant || m == -__builtin_inff()) return Var(v);
+    for (int i = 0; i < n; i += 2) {
+        const bool two = i + 1 < n;
+        push_bits(a[i].id, two ? a[i + 1].id : -1, float_bits(::gmmvi_vector::logsumexp_partial(a[i].v, m, s)),
+                  two ? float_bits(::gmmvi_vector::logsumexp_partial(a[i + 1].v, m, s)) : 0);
+    }
+    return Var(v, push_vector(::gmmvi_vector::NODES, -1, n, ::gmmvi_vector::LOGSUMEXP, 0));
+}
+#endif
+
+// The vector record v at record index r with adjoint w: adds w * d node / d x[first + i] into g[(first + i) * g_stride], i
+// ascending; a node-array record also adds w * d node / d entry i into the adjoint of every entry that is not a constant, from
+// its payload in the slots below r.  x: the lane's inputs.  -> the slots the record spans, which the sweep steps back over.
+GMMVI_TAPE_FN int sweep_vector(const Rec4& v, float w, int r, int D, RecPtr rp, AdjPtr ap, size_t stride, const float* x, float* g,
+                               size_t g_stride) {
     const int code = -2 - v.x, kind = code & 3, n = code >> 2;
+#ifdef GMMVI_TAPE_NODES
+    if (kind == ::gmmvi_vector::NODES) {
+        const int slots = (n + 1) >> 1;
+        const bool wdot = v.z == ::gmmvi_vector::WDOT;
+        for (int i = 0; i < n; ++i) {
+            const Rec4 e = rp[(size_t)(r - slots + (i >> 1)) * stride];
+            const int id = i & 1 ? e.y : e.x;
+            float d = bits_float(i & 1 ? e.w : e.z) * w;              // gmmvi_logsumexp: p_i w, the entry's share
+            if (wdot) {
+                g[(size_t)(v.y + i) * g_stride] += d;                   // h[i].v w, the input's share; the entry's is x[first + i] w
+                d = x[v.y + i] * w;
+            }
+            if (id >= 0) {
+                if (id < D) g[(size_t)id * g_stride] += d; else ap[(size_t)(id - D) * stride] += d;
+            }
+        }
+        return 1 + slots;
+    }
+#endif
     x += v.y;
     g += (size_t)v.y * g_stride;
     if (kind == ::gmmvi_vector::SUMSQ) {
         const float center = bits_float(v.z);
         for (int i = 0; i < n; ++i) g[(size_t)i * g_stride] += 2.f * (x[i] - center) * w;
-        return;
+        return 1;
     }
     union { const float* p; int i[2]; } u; u.i[0] = v.z; u.i[1] = v.w;
     const float* c = u.p;
@@ -263,6 +327,7 @@ GMMVI_TAPE_FN void sweep_vector(const Rec4& v, float w, const float* x, float* g
     } else {
         for (int i = 0; i < n; ++i) g[(size_t)i * g_stride] += 2.f * (x[i] - c[i]) * w;
     }
+    return 1;
 }
 
 // The sweep of one lane: adds d out / d x[i] into g[i * g_stride] for every input i, walking the records from the output's own back
@@ -291,8 +356,7 @@ GMMVI_TAPE_FN void sweep(const Var& out, int D, RecPtr rp, AdjPtr ap, size_t str
             }
             if (--r < 0) return;
         }
-        sweep_vector(v, w, x, g, g_stride);
-        --r;
+        r -= sweep_vector(v, w, r, D, rp, ap, stride, x, g, g_stride);
     }
 }
 

@@ -11,6 +11,15 @@ R"GMMVI_VECTOR(
 //
 // The order: four partial sums, element i into partial i mod 4 by one fused multiply-add each (fmaf, whatever the contraction
 // setting of the compiler), i ascending; the result is (s0 + s1) + (s2 + s3).  n <= 0 gives +0.
+//
+// Two primitives take an array of the mode's number type T (a float here, a Dual or a Var in the gradient modes), typically one
+// local to the user's function:
+//     gmmvi_wdot(x, first, h, n)        sum over i < n of h[i] * x[first + i], h a const T*
+//     gmmvi_logsumexp(a, n)             log of the sum over i < n of exp(a[i]), a a const T*
+// Their values come from the two templates over an accessor below (entry i of the array as a float), which all three number
+// types call: gmmvi_wdot in the order above, so that on floats it has the bits of gmmvi_dot; gmmvi_logsumexp as m + logf(s) with
+// m the maximum by fmaxf, i ascending from -inf, and s the sum of expf(a[i] - m) in four partial sums by plain adds, merged as
+// above.  m == -inf (n <= 0, every entry -inf; fmaxf drops NaNs, so an array of NaNs as well) gives -inf and no partials.
 namespace gmmvi_vector {
 
 enum Kind { DOT = 0, SQDIST = 1, SUMSQ = 2 };                      // the order of _lib.VECTOR_OPS, and the kind of a tape record
@@ -63,8 +72,66 @@ __host__ __device__ inline float sumsq_value(const float* x, int n, float center
     return (s0 + s1) + (s2 + s3);
 }
 
+enum NodeOp { WDOT = 0, LOGSUMEXP = 1 };                           // the order of _lib.NODE_OPS, and z of a node-array record's header
+constexpr int NODES = 3;                                           // the kind of the tape's node-array record
+
+struct FloatAt {                                                   // the accessor of a float array
+    const float* p;
+    __host__ __device__ float operator()(int i) const { return p[i]; }
+};
+
+// x: the first element of the range; h(i): the value of entry i.  The order of dot_value.
+template <class At>
+__host__ __device__ inline float wdot_value(const float* x, At h, int n) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {
+        s0 = ::fmaf(h(i), x[i], s0);
+        s1 = ::fmaf(h(i + 1), x[i + 1], s1);
+        s2 = ::fmaf(h(i + 2), x[i + 2], s2);
+        s3 = ::fmaf(h(i + 3), x[i + 3], s3);
+    }
+    if (i < n) s0 = ::fmaf(h(i), x[i], s0);
+    if (i + 1 < n) s1 = ::fmaf(h(i + 1), x[i + 1], s1);
+    if (i + 2 < n) s2 = ::fmaf(h(i + 2), x[i + 2], s2);
+    return (s0 + s1) + (s2 + s3);
+}
+
+// -> m + logf(s); m and s go back to the caller for the partials.  m == -inf: -> -inf, s = 0, and there are no partials.
+template <class At>
+__host__ __device__ inline float logsumexp_value(At a, int n, float& m, float& s) {
+    const float lowest = -__builtin_inff();
+    m = lowest;
+    s = 0.f;
+    for (int i = 0; i < n; ++i) m = ::fmaxf(m, a(i));
+    if (m == lowest) return lowest;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {
+        s0 += ::expf(a(i) - m);
+        s1 += ::expf(a(i + 1) - m);
+        s2 += ::expf(a(i + 2) - m);
+        s3 += ::expf(a(i + 3) - m);
+    }
+    if (i < n) s0 += ::expf(a(i) - m);
+    if (i + 1 < n) s1 += ::expf(a(i + 1) - m);
+    if (i + 2 < n) s2 += ::expf(a(i + 2) - m);
+    s = (s0 + s1) + (s2 + s3);
+    return m + ::logf(s);
+}
+
+// d logsumexp / d a[i], from the m and s of logsumexp_value: both gradient modes form their partials here
+__host__ __device__ inline float logsumexp_partial(float a, float m, float s) { return ::expf(a - m) / s; }
+
 }  // namespace gmmvi_vector
 
+__host__ __device__ inline float gmmvi_wdot(const float* x, int first, const float* h, int n) {
+    return gmmvi_vector::wdot_value(x + first, gmmvi_vector::FloatAt{h}, n);
+}
+__host__ __device__ inline float gmmvi_logsumexp(const float* a, int n) {
+    float m, s;
+    return gmmvi_vector::logsumexp_value(gmmvi_vector::FloatAt{a}, n, m, s);
+}
 __host__ __device__ inline float gmmvi_dot(const float* x, int first, const float* c, int n) {
     return gmmvi_vector::dot_value(x + first, c, n);
 }

@@ -5,6 +5,7 @@
 #include "common.h"
 
 #define GMMVI_TAPE_NO_KERNELS
+#define GMMVI_TAPE_NODES 1                                       // the overloads and the sweep of the node-array record
 #include "build/custom_target_special_text.inc"
 #include "build/custom_target_tape_text.inc"
 
@@ -153,6 +154,58 @@ extern "C" int gmmvi_tape_probe_vector(int op, const float* x, int D, int first,
         default:
             return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_vector: unknown operation " + std::to_string(op));
     }
+    *value = r.v;
+    *records = gmmvi_tape::count();
+    for (int i = 0; i < D; ++i) grad[i] = 0.f;
+    gmmvi_tape::sweep(r, D, (gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, x, grad, 1);
+    return GMMVI_OK;
+}
+
+// one primitive on an array of nodes (gmmvi_wdot, gmmvi_logsumexp), in the order of _lib.NODE_OPS: the array of
+// gmmvi_autodiff_probe_nodes, one tanh record per entry that is not a constant; the value, the lane's record count (those
+// records and the 1 + ceil(n / 2) slots of the node-array record), and the gradient [D] that gmmvi_tape::sweep leaves at stride 1
+extern "C" int gmmvi_tape_probe_nodes(int op, const float* x, int D, int first, int n, int src, int every, float* value, float* grad,
+                                      int* records) {
+    constexpr int kMax = 64;
+    if (!x || !value || !grad || !records || op < 0 || op > gmmvi_vector::LOGSUMEXP || D < 1 || first < 0 || n < 0 || src < 0 ||
+        every < 0 || n > kMax || src > D - n || first > D - n)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_nodes: needs a known operation, x, value, grad, records, D >= 1, "
+                                                  "0 <= n <= 64, 0 <= first, 0 <= src, 0 <= every, first + n <= D and src + n <= D");
+    constexpr int kCap = kMax + 1 + kMax / 2;                       // a record per entry, the header and its payload
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, D};
+    gmmvi_tape::count() = 0;
+    const gmmvi_tape::Input in{x};
+    Var h[kMax];
+    for (int i = 0; i < n; ++i)
+        h[i] = every > 0 && i % every == every - 1 ? Var(::tanhf(x[src + i])) : tanh(in[src + i]);
+    const Var r = op == gmmvi_vector::WDOT ? gmmvi_wdot(in, first, h, n) : gmmvi_logsumexp(h, n);
+    *value = r.v;
+    *records = gmmvi_tape::count();
+    for (int i = 0; i < D; ++i) grad[i] = 0.f;
+    gmmvi_tape::sweep(r, D, (gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, x, grad, 1);
+    return GMMVI_OK;
+}
+
+// the same call on an array whose entries are the input nodes themselves, h[i] = x[src + i] (no record of their own): the
+// gradient of gmmvi_logsumexp is then its partials p_i bit for bit, and x may hold -inf
+extern "C" int gmmvi_tape_probe_nodes_inputs(int op, const float* x, int D, int first, int n, int src, float* value, float* grad,
+                                             int* records) {
+    constexpr int kMax = 64;
+    if (!x || !value || !grad || !records || op < 0 || op > gmmvi_vector::LOGSUMEXP || D < 1 || first < 0 || n < 0 || src < 0 ||
+        n > kMax || src > D - n || first > D - n)
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_nodes_inputs: needs a known operation, x, value, grad, records, "
+                                                  "D >= 1, 0 <= n <= 64, 0 <= first, 0 <= src, first + n <= D and src + n <= D");
+    constexpr int kCap = 1 + kMax / 2;
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, D};
+    gmmvi_tape::count() = 0;
+    const gmmvi_tape::Input in{x};
+    Var h[kMax];
+    for (int i = 0; i < n; ++i) h[i] = in[src + i];
+    const Var r = op == gmmvi_vector::WDOT ? gmmvi_wdot(in, first, h, n) : gmmvi_logsumexp(h, n);
     *value = r.v;
     *records = gmmvi_tape::count();
     for (int i = 0; i < D; ++i) grad[i] = 0.f;

@@ -406,6 +406,26 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  * i ascending, then (s0 + s1) + (s2 + s3).  The derivatives are closed forms: c[k], 2 (x - c[k]), 2 (x - center) by
  * x[first + k], nothing by c.  Forward mode: the tangents of a pass are 16 loads, there is no loop over n with tangents.  Tape
  * modes: one record per call whatever n is (below).
+ * Two primitives take an array of T, the number type of the mode (float on value calls and in the hand-written mode, the dual,
+ * the tape node); the overloads of the gradient modes are found by argument-dependent lookup on the array's element type:
+ *   - gmmvi_wdot(X x, int first, const T* h, int n):            sum over i < n of h[i] * x[first + i];
+ *   - gmmvi_logsumexp(const T* a, int n):                       log of the sum over i < n of exp(a[i]).
+ * gmmvi_wdot: entries of h may be constants; n <= 0 gives the constant 0 (zero tangents, no record); 0 <= first and
+ * first + n <= D are the caller's duty.  The value has the order of gmmvi_dot (fmaf(h[i].value, x[first + i], s), four partial
+ * sums), from one function for all three number types: a value call and a gradient call agree bit for bit, and on floats the
+ * result has the bits of gmmvi_dot(x, first, h, n).  THERE IS NO LIFETIME RULE FOR h (or for a): unlike c of gmmvi_dot, what
+ * the reverse sweep needs is copied into the record, so an array local to the user's function is the normal case.  A const
+ * float* in the place of x does not compile in the gradient modes.
+ * gmmvi_logsumexp: m = the maximum by fmaxf, i ascending from -inf; s = the sum of expf(a[i] - m) in four partial sums by plain
+ * adds, element i into partial i mod 4, merged (s0 + s1) + (s2 + s3); the result is m + logf(s), again from one function for
+ * all three number types.  The partials p_i = expf(a[i] - m) / s come from one helper in both gradient modes.  m == -inf (n <= 0
+ * or every entry -inf) gives the constant -inf: zero tangents, no record.  If every a[i] is a constant the result is a constant.
+ * Any other non-finite maximum is outside the contract and cannot fault (no index depends on a value); what it yields: a +inf
+ * entry makes the value and every partial NaN; a NaN entry beside finite ones is dropped from the maximum and makes the value
+ * and every partial NaN through s; an array of NaNs alone has m == -inf and gives the constant -inf.
+ * Forward mode: tangent j of gmmvi_wdot is the sum over i of x[first + i] * h[i].d[j], by fmaf, i ascending, plus h[k].v for
+ * k = x.first + j - first where 0 <= k < n; tangent j of gmmvi_logsumexp is the sum over i of p_i * a[i].d[j], by fmaf.  One
+ * pass over n per call.  Tape modes: one node-array record per call, 1 + ceil(n / 2) slots (below).
  * The gradient takes ceil(D / W) passes of the dual instantiation, W = GMMVI_CUSTOM_AUTODIFF_TANGENTS, pass `first` writing
  * grad[first + j] for first + j < D; the value is that of the first pass.  That is ceil(D / W) * (1 + W) value evaluations per
  * sample, so a gradient call through such a handle is capped at GMMVI_CUSTOM_AUTODIFF_MAX_DIM; a value call is not. */
@@ -435,6 +455,17 @@ int gmmvi_autodiff_probe_extra(int op, float a, float da, float* value, float* t
  * array, D < 1, first < 0, seed_first < 0 or first + n > D: GMMVI_ERR_ARG. */
 int gmmvi_autodiff_probe_vector(int op, const float* x, int D, int first, int n, const float* c, float center, int seed_first,
                                 float* value, float* tangents);
+/* One primitive on an array of duals, in the pass seeded at seed_first (gmmvi_amd/_lib.py NODE_OPS names the operations in
+ * index order: gmmvi_wdot, gmmvi_logsumexp).  The array is h[i] = tanh(x[src + i]) for i < n; where every > 0 and
+ * i % every == every - 1 the entry is the constant tanhf(x[src + i]) instead (every = 1: all constants).  The call is
+ * gmmvi_wdot(x, first, h, n) or gmmvi_logsumexp(h, n); *value and tangents[GMMVI_CUSTOM_AUTODIFF_TANGENTS] as above.  An
+ * unknown op, a NULL array, D < 1, n > 64, src + n > D, first + n > D or a negative argument: GMMVI_ERR_ARG. */
+int gmmvi_autodiff_probe_nodes(int op, const float* x, int D, int first, int n, int src, int every, int seed_first, float* value,
+                               float* tangents);
+/* The same call on an array whose entries are the inputs themselves, h[i] = x[src + i], which may be -inf: the tangents of
+ * gmmvi_logsumexp are then its partials p_i bit for bit.  The same arguments are GMMVI_ERR_ARG. */
+int gmmvi_autodiff_probe_nodes_inputs(int op, const float* x, int D, int first, int n, int src, int seed_first, float* value,
+                                      float* tangents);
 
 /* ---- user-defined targets summed over a data set --------------------------------------------------------------------------------
  * Posteriors of the shape  log p(x) = log prior(x) + sum over the data rows r of log p(data_r | x):  the source defines one
@@ -540,6 +571,19 @@ int gmmvi_target_custom_data_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_targ
  * that meets such a record with adjoint w adds c[i] w, 2 (x[first + i] - c[i]) w or 2 (x[first + i] - center) w to the adjoint of
  * input first + i for i < n, i ascending; it reads c and the lane's x then, after the user's function has returned.  A lane
  * sweeps the kind of its own record, whatever the other lanes of its wave hold at that record index.
+ * Kind 3 is the node-array record of gmmvi_wdot and gmmvi_logsumexp, which spans 1 + ceil(n / 2) slots.  The payload comes
+ * first: slot j = {id of entry 2 j, id of entry 2 j + 1 or -1, 32 bits for each entry}, the bits h[i].v for gmmvi_wdot and the
+ * partial p_i for gmmvi_logsumexp.  The header stands behind its payload, because the sweep walks backwards:
+ * {ia = -2 - (4 n + 3), ib = first or -1, the operation (0 gmmvi_wdot, 1 gmmvi_logsumexp), 0}.  The result's node id is the
+ * header's; no node refers to a payload slot, and the adjoint zeroed for it is never read.  The loop forms cost 2 n and n - 1
+ * records.  Beyond the capacity nothing is stored and the count advances slot by slot, so the needed length is in slots and the
+ * relaunch is the usual one.  On a header with adjoint w, i ascending: gmmvi_wdot adds h[i].v w to the adjoint of input
+ * first + i and, for an entry that is not a constant, x[first + i] w to the entry's adjoint (the gradient's entry if the entry
+ * is an input); gmmvi_logsumexp adds p_i w to the adjoint of every entry that is not a constant.  Then the sweep steps over the
+ * payload.
+ * The overloads on tape nodes and this branch of the sweep are compiled only into a text that names gmmvi_wdot or gmmvi_logsumexp
+ * (the library searches the source for the two names and defines GMMVI_TAPE_NODES): the kernels of every other source are what
+ * they were without the two primitives.  A text that builds the name by token pasting therefore does not compile on the tape.
  * Kernels: one lane is one sample, one wave per workgroup.  The lane records the user's function (every store guarded by the
  * capacity; beyond it the value stays right and the count keeps counting), then, in the same launch, seeds the output's adjoint
  * with 1 and walks its own records from the output back to the first.  Adjoints of inputs add up in the lane's own row of
@@ -595,6 +639,15 @@ int gmmvi_tape_probe_extra(int op, float a, int a_is_const, float* value, float*
  * [first, first + n)).  An unknown op, a NULL array, D < 1, first < 0 or first + n > D: GMMVI_ERR_ARG. */
 int gmmvi_tape_probe_vector(int op, const float* x, int D, int first, int n, const float* c, float center, float* value, float* grad,
                             int* records);
+/* One primitive on an array of nodes, op and the array as for gmmvi_autodiff_probe_nodes (an entry that is not a constant is
+ * one tanh record): *value; *records, the lane's count: the entries that are not constants plus the 1 + ceil(n / 2) slots of
+ * the node-array record, the latter left out where the result is a constant; grad[D], what the sweep of the tape modes leaves
+ * from the result with adjoint 1.  The same arguments are GMMVI_ERR_ARG. */
+int gmmvi_tape_probe_nodes(int op, const float* x, int D, int first, int n, int src, int every, float* value, float* grad,
+                           int* records);
+/* The same call on an array whose entries are the input nodes themselves, h[i] = x[src + i] (they make no record, so *records
+ * is 1 + ceil(n / 2) or 0), which may be -inf: the gradient of gmmvi_logsumexp is then its partials p_i bit for bit. */
+int gmmvi_tape_probe_nodes_inputs(int op, const float* x, int D, int first, int n, int src, float* value, float* grad, int* records);
 
 /* ---- targets summed over a data set, differentiated on a tape ------------------------------------------------------------------
  * The source of the data mode, unchanged (gmmvi_user_row and gmmvi_user_prior, templates over the number type; compiled with

@@ -37,8 +37,9 @@ def report(ctx):
     return {f[0]: float(f[2]) for f in (line.split() for line in buf.value.decode().splitlines()) if len(f) >= 3}
 
 
-def timed_us(ctx, fn, seconds):
-    """-> (median microseconds of a call, by kernel tag and in total; timed calls)."""
+def timed_us(ctx, fn, seconds, totals=None):
+    """-> (median microseconds of a call, by kernel tag and in total; timed calls).  totals: a list that receives every timed
+    call's total in microseconds."""
     fn()
     ctx.check(ctx.lib.gmmvi_profile_enable(ctx.handle, 1))
     calls, t0 = [], time.time()
@@ -48,6 +49,8 @@ def timed_us(ctx, fn, seconds):
             calls.append(report(ctx))
     finally:
         ctx.check(ctx.lib.gmmvi_profile_enable(ctx.handle, 0))
+    if totals is not None:
+        totals.extend(round(sum(c.values()) * 1e3, 1) for c in calls)
     tags = sorted(calls[0])
     by_tag = {t: round(statistics.median(c[t] for c in calls) * 1e3, 1) for t in tags}
     return round(statistics.median(sum(c.values()) for c in calls) * 1e3, 1), by_tag, len(calls)
