@@ -2,6 +2,7 @@
 // launch sequences over the batched contraction (blocked_gemm.h) and one-workgroup-per-component kernels (blocked_factor.h).
 #include "blocked_gemm.h"
 #include "blocked_factor.h"
+#include "trust_region.h"
 
 // update_kl.hip UKL_TAIL_MIN: a column of the whitened M whose tail sum of squares is at most this counts as already tridiagonal
 // (negligible against the unit diagonal of B = I + M / eta; in the fp32 subnormal range 1 / (nrm^2 - alpha x1) overflows)
@@ -459,49 +460,7 @@ const TridiagReg blk_tridiag_instances[] = {BLK_TRIDIAG_ROW(64, 8, 1),   BLK_TRI
                                             BLK_TRIDIAG_ROW(256, 32, 4), BLK_TRIDIAG_ROW(304, 38, 5), BLK_TRIDIAG_ROW(320, 40, 5)};
 #undef BLK_TRIDIAG_ROW
 
-// KL(eta) from the tridiagonal form (update_kl.hip kl_tridiag), pivots kept in a global scratch column per lane
-__device__ __forceinline__ float blk_kl_tridiag(int D, const float* td, const float* te, const float* wt, float* scratch,
-                                                float eta) {
-    const int lane = threadIdx.x;
-    const float inv = 1.f / eta;
-    float* dcol = scratch + lane;
-    float dprev = 1.f, cprev = 0.f, logdet = 0.f;
-    bool ok = true;
-    for (int i = 0; i < D; ++i) {
-        const float a = fmaf(td[i], inv, 1.f);
-        float d = a, c = wt[i];
-        if (i > 0) {
-            const float b = te[i - 1] * inv;
-            const float r = b / dprev;
-            d = fmaf(-b, r, a);
-            c = fmaf(-r, cprev, c);
-        }
-        ok = ok && (d > 0.f);
-        logdet += __logf(d);
-        dcol[(size_t)i * 64] = d;
-        dcol[(size_t)(D + i) * 64] = c;
-        dprev = d; cprev = c;
-    }
-    float dnext = 1.f, ynext = 0.f, tr = 0.f, yy = 0.f;
-    for (int i = D - 1; i >= 0; --i) {
-        const float a = fmaf(td[i], inv, 1.f);
-        const float d = dcol[(size_t)i * 64], c = dcol[(size_t)(D + i) * 64];
-        float delta = a, y = c / d;
-        if (i < D - 1) {
-            const float b = te[i] * inv;
-            delta = fmaf(-b, b / dnext, a);
-            y = (c - b * ynext) / d;
-        }
-        tr += 1.f / (d + delta - a);
-        yy = fmaf(y, y, yy);
-        dnext = delta; ynext = y;
-    }
-    float kl = 0.5f * (logdet - (float)D + tr + yy * inv * inv);
-    if (!ok || !(kl == kl)) kl = FLT_MAX;
-    return kl;
-}
-
-// bracketing search (:335-429) on the tridiagonal form, 63 nodes of the bisection tree per round (update_kl.hip);
+// bracketing search (:335-429) on the tridiagonal form, 63 nodes of the bisection tree per round (as in update_kl.hip);
 // state[k] = (eta*, success, KL(eta*), probes)
 __global__ __launch_bounds__(64) void blk_search_kernel(int D, const float* __restrict__ td_all, const float* __restrict__ te_all,
                                                         const float* __restrict__ wt_all, const float* __restrict__ stepsizes,
@@ -541,7 +500,7 @@ __global__ __launch_bounds__(64) void blk_search_kernel(int D, const float* __re
         const float neta = 0.5f * (nub + nlb);
         const float e_eta = expf(neta);
         const float ndiff = fminf(expf(nub) - e_eta, e_eta - expf(nlb));
-        const float nkl = (t >= 1) ? blk_kl_tridiag(D, td, te, wt, scratch, e_eta) : 0.f;
+        const float nkl = (t >= 1) ? tr_kl_tridiag<0, false>(D, td, te, wt, scratch + t, e_eta) : 0.f;
         int n = 1;
         for (int level = 0; level < 6 && !done && iters < 1000; ++level, ++iters) {
             const float diff = __shfl(ndiff, n), klv = __shfl(nkl, n), eta = __shfl(neta, n);
@@ -558,7 +517,8 @@ __global__ __launch_bounds__(64) void blk_search_kernel(int D, const float* __re
     bool success = (lo == hi);
     float kl_val = -1.f;
     if (success) {
-        kl_val = (eta_star == lo && kl_ub >= 0.f) ? kl_ub : __shfl(blk_kl_tridiag(D, td, te, wt, scratch, eta_star), 0);
+        kl_val = (eta_star == lo && kl_ub >= 0.f)
+                     ? kl_ub : __shfl(tr_kl_tridiag<0, false>(D, td, te, wt, scratch + t, eta_star), 0);
         success = kl_val < FLT_MAX;
     }
     if (t == 0) {
@@ -637,15 +597,8 @@ __global__ __launch_bounds__(704) void blk_upd_final_kernel(int D, int mode, con
         }
     }
     if (t == 0) {
-        if (mode == 0) {
-            last_eta[k] = success ? eta_star : -1.f;
-            if (kl_out) kl_out[k] = success ? kl_val : -1.f;
-            if (nprobes_out) nprobes_out[k] = (int32_t)state[4 * k + 3];
-        }
-        const float old = l2[k];
-        l2[k] = success ? fmaxf(0.5f * old, l2_init) : fminf(1e-6f, 10.f * old);
-        num_updates[k] += 1.f;
-        if (success_out) success_out[k] = success ? 1 : 0;
+        if (mode == 0) tr_report_search(k, success, eta_star, kl_val, (int32_t)state[4 * k + 3], last_eta, kl_out, nprobes_out);
+        tr_finish_bookkeeping(k, success, l2_init, l2, num_updates, success_out);
     }
 }
 

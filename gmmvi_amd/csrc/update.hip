@@ -9,6 +9,7 @@
 // reference's "NaN in the factor" branch (:320-324, :493).
 #include "common.h"
 #include "blocked.h"
+#include "trust_region.h"
 #include <cfloat>
 
 namespace {
@@ -209,16 +210,6 @@ __device__ void store_component(const Lds& s, float* L_out, float* mu_out) {
     if (t < D) mu_out[t] = s.mun[t];
 }
 
-__device__ void finish_bookkeeping(int k, bool success, float l2_init, float* l2, float* num_updates,
-                                   int32_t* success_out) {
-    if (threadIdx.x == 0) {
-        const float old = l2[k];
-        l2[k] = success ? fmaxf(0.5f * old, l2_init) : fminf(1e-6f, 10.f * old);        // :520-523 (min on failure)
-        num_updates[k] += 1.f;                                                           // :519
-        if (success_out) success_out[k] = success ? 1 : 0;
-    }
-}
-
 __global__ __launch_bounds__(64) void update_kl_kernel(int D, float* __restrict__ means, float* __restrict__ chols,
                                                        const float* __restrict__ H_neg, const float* __restrict__ g_neg,
                                                        const float* __restrict__ stepsizes, float temperature,
@@ -279,11 +270,9 @@ __global__ __launch_bounds__(64) void update_kl_kernel(int D, float* __restrict_
     }
     if (success) store_component(s, Lg, mug);                                             // :499-504 (else keep old)
     if (t == 0) {
-        last_eta[k] = success ? eta_star : -1.f;                                          // :504,:511,:524
-        if (kl_out) kl_out[k] = success ? kl_val : -1.f;
-        if (nprobes_out) nprobes_out[k] = probes;
+        tr_report_search(k, success, eta_star, kl_val, probes, last_eta, kl_out, nprobes_out);
+        tr_finish_bookkeeping(k, success, l2_init, l2, num_updates, success_out);
     }
-    finish_bookkeeping(k, success, l2_init, l2, num_updates, success_out);
 }
 
 // mode 0: direct (:97-141); mode 1: iBLR (:160-223)
@@ -380,7 +369,7 @@ __global__ __launch_bounds__(64) void update_plain_kernel(int mode, int D, float
         success = !wave_any(bad);
     }
     if (success) store_component(s, Lg, mug);
-    finish_bookkeeping(k, success, l2_init, l2, num_updates, success_out);
+    if (t == 0) tr_finish_bookkeeping(k, success, l2_init, l2, num_updates, success_out);
 }
 
 size_t update_lds_bytes(int D) { return ((size_t)5 * D * (D + 1) + 6 * D) * sizeof(float); }

@@ -16,6 +16,7 @@
 #include "blocked.h"
 #include "wave_reduce.h"
 #include "stein_finalize.h"
+#include "trust_region.h"
 #include <cfloat>
 #include <type_traits>
 
@@ -109,53 +110,6 @@ __device__ void carve(Ws& s, float* sm, int D) {
 }
 
 size_t lds_bytes(int D) { return ((size_t)3 * D * (D + 1) + 9 * D + (size_t)2 * D * 64) * sizeof(float); }
-
-// KL(eta) from the tridiagonal form; every lane may evaluate a different eta (scratch column = lane).  The two recurrences
-// are chains of D dependent steps with a reciprocal each: v_rcp_f32 (1 ulp) instead of the IEEE division sequence halves the
-// search phase (D = 20: 5.1 -> 3.8 us); accept / reject decisions and probe counts of the parity tests are unchanged.
-template <int DC>
-__device__ __forceinline__ float kl_tridiag(const Ws& s, float eta) {
-    const int D = DC > 0 ? DC : s.D, lane = threadIdx.x;
-    const float inv = 1.f / eta;
-    float* dcol = s.pr + lane;                 // d_i at [i][lane], c_i at [D + i][lane]
-    float dprev = 1.f, cprev = 0.f, logdet = 0.f;
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < D; ++i) {
-        const float a = fmaf(s.td[i], inv, 1.f);
-        float d = a, c = s.wt[i];
-        if (i > 0) {
-            const float b = s.te[i - 1] * inv;
-            const float r = b * __builtin_amdgcn_rcpf(dprev);
-            d = fmaf(-b, r, a);
-            c = fmaf(-r, cprev, c);
-        }
-        ok = ok && (d > 0.f);
-        logdet += __logf(d);
-        dcol[i * 64] = d;
-        dcol[(D + i) * 64] = c;
-        dprev = d; cprev = c;
-    }
-    float dnext = 1.f, ynext = 0.f, tr = 0.f, yy = 0.f;
-#pragma unroll
-    for (int i = D - 1; i >= 0; --i) {
-        const float a = fmaf(s.td[i], inv, 1.f);
-        const float d = dcol[i * 64], c = dcol[(D + i) * 64];
-        const float rd = __builtin_amdgcn_rcpf(d);
-        float delta = a, y = c * rd;
-        if (i < D - 1) {
-            const float b = s.te[i] * inv;
-            delta = fmaf(-b, b * __builtin_amdgcn_rcpf(dnext), a);
-            y = (c - b * ynext) * rd;
-        }
-        tr += __builtin_amdgcn_rcpf(d + delta - a);
-        yy = fmaf(y, y, yy);
-        dnext = delta; ynext = y;
-    }
-    float kl = 0.5f * (logdet - (float)D + tr + yy * inv * inv);
-    if (!ok || !(kl == kl)) kl = FLT_MAX;
-    return kl;
-}
 
 // DC > 0: dimension known at compile time (inner loops unrolled, LDS reads issued in batches); DC == 0: generic.
 template <int DC, int NW>
@@ -511,7 +465,9 @@ __global__ __launch_bounds__(64 * NW) void update_kl_fast_kernel(int Drt, float*
     }
 
     UKL_STAMP(2);                                      // tridiagonal form done
-    // ---- speculative bisection: 63 tree nodes (6 levels) per round, one lane per node ------------------------------------
+    // ---- speculative bisection: 63 tree nodes (6 levels) per round, one lane per node.  KL(eta) is tr_kl_tridiag with
+    // v_rcp_f32 (1 ulp) instead of the IEEE division sequence: it halves the search phase (D = 20: 5.1 -> 3.8 us); accept /
+    // reject decisions and probe counts of the parity tests are unchanged ---------------------------------------------------
     const float eps = stepsizes[k];
     const float last = last_eta[k];
     float lb, ub;
@@ -533,7 +489,8 @@ __global__ __launch_bounds__(64 * NW) void update_kl_fast_kernel(int Drt, float*
         const float neta = 0.5f * (nub + nlb);
         const float e_eta = expf(neta);
         const float ndiff = fminf(expf(nub) - e_eta, e_eta - expf(nlb));                  // :401
-        const float nkl = (t >= 1) ? kl_tridiag<DC>(s, e_eta) : 0.f;                           // :407
+        const float nkl =                                                                  // :407
+            (t >= 1) ? tr_kl_tridiag<DC, true>(D, s.td, s.te, s.wt, s.pr + t, e_eta) : 0.f;
         int n = 1;
         for (int level = 0; level < 6 && !done && iters < 1000; ++level, ++iters) {
             const float diff = __shfl(ndiff, n), klv = __shfl(nkl, n), eta = __shfl(neta, n);
@@ -554,7 +511,8 @@ __global__ __launch_bounds__(64 * NW) void update_kl_fast_kernel(int Drt, float*
     if (success) {
         // :480-482 evaluates KL at eta*; when eta* is the accepted bracket end (the usual case, eta* = lo >= temperature)
         // that is the value the search already holds for exactly this eta
-        kl_val = (eta_star == lo && kl_ub >= 0.f) ? kl_ub : __shfl(kl_tridiag<DC>(s, eta_star), 0);
+        kl_val = (eta_star == lo && kl_ub >= 0.f)
+                     ? kl_ub : __shfl(tr_kl_tridiag<DC, true>(D, s.td, s.te, s.wt, s.pr + t, eta_star), 0);
         success = kl_val < FLT_MAX;                                                        // :488
     }
     if (DC > 0) {
@@ -888,13 +846,8 @@ __global__ __launch_bounds__(64 * NW) void update_kl_fast_kernel(int Drt, float*
     kl_out = nullptr;
 #endif
     if (t == 0) {
-        last_eta[k] = success ? eta_w : -1.f;                                              // :504,:511,:524
-        if (kl_out) kl_out[k] = success ? kl_w : -1.f;
-        if (nprobes_out) nprobes_out[k] = probes_w;
-        const float old = l2[k];
-        l2[k] = success ? fmaxf(0.5f * old, l2_init) : fminf(1e-6f, 10.f * old);           // :520-523 (min on failure)
-        num_updates[k] += 1.f;                                                             // :519
-        if (success_out) success_out[k] = success ? 1 : 0;
+        tr_report_search(k, success, eta_w, kl_w, probes_w, last_eta, kl_out, nprobes_out);
+        tr_finish_bookkeeping(k, success, l2_init, l2, num_updates, success_out);
     }
 }
 

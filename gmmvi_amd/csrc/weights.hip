@@ -204,6 +204,34 @@ __device__ __forceinline__ float weights_kl_reg(float eta, float beta, const flo
     return wsum(kl);
 }
 
+// The bisection of the trust-region weight update (:232-260, bracket :276-277) over kl_at(eta) -> KL(new || old), which also leaves
+// the new log weights of its eta with the caller.  On return they are those of the accepted eta; updated = false (and
+// (kl, eta) = (-1, -1)) when no probe was inside the bound.  kl_at may synchronise the wavefront: entered by all 64 lanes, every
+// decision on a wave-uniform value.  (Not the component search of trust_region.h: other bracket, cap and stop rule.)
+template <class KlAt>
+__device__ __forceinline__ void weights_bisect(float bound, KlAt&& kl_at, float& kl, float& eta, bool& updated) {
+    float lb = -45.f, ub = 45.f;                                                          // :276-277
+    float log_eta = 0.5f * (ub + lb);
+    bool ub_ok = false;
+    for (int it = 0; it < 50; ++it) {                                                     // :232
+        eta = expf(log_eta);
+        if (fabsf(expf(ub) - expf(lb)) < 1e-1f) break;                                    // :234-236
+        kl = kl_at(eta);                                                                  // :238
+        if (fabsf(bound - kl) < 1e-1f * bound) { lb = ub; break; }                        // :240-243
+        if (bound > kl) { ub = log_eta; ub_ok = true; } else { lb = log_eta; }            // :245-249
+        log_eta = 0.5f * (ub + lb);
+    }
+    if (lb == ub) {
+        // :252-253 keep the last evaluated weights
+    } else if (ub_ok) {
+        eta = expf(ub);
+        kl = kl_at(eta);                                                                  // :256-258
+    } else {
+        updated = false;                                                                  // :260
+        kl = -1.f; eta = -1.f;
+    }
+}
+
 // the bisection of the trust-region update (:232-260) with the lane's elements in registers
 template <int NE>
 __device__ __forceinline__ void weights_search_reg(int K, float beta, float bound, const float* lw_s, const float* E_s, float* nl,
@@ -218,26 +246,8 @@ __device__ __forceinline__ void weights_search_reg(int K, float beta, float boun
         E[e] = h[e] ? E_s[t + 64 * e] : 0.f;
         v[e] = lw[e];                                                                     // nl starts as the old weights
     }
-    float lb = -45.f, ub = 45.f;                                                          // :276-277
-    float log_eta = 0.5f * (ub + lb);
-    bool ub_ok = false;
-    for (int it = 0; it < 50; ++it) {                                                     // :232
-        eta = expf(log_eta);
-        if (fabsf(expf(ub) - expf(lb)) < 1e-1f) break;                                    // :234-236
-        kl = weights_kl_reg<NE>(eta, beta, lw, E, h, v);                                  // :238
-        if (fabsf(bound - kl) < 1e-1f * bound) { lb = ub; break; }                        // :240-243
-        if (bound > kl) { ub = log_eta; ub_ok = true; } else { lb = log_eta; }            // :245-249
-        log_eta = 0.5f * (ub + lb);
-    }
-    if (lb == ub) {
-        // :252-253 keep the last evaluated weights
-    } else if (ub_ok) {
-        eta = expf(ub);
-        kl = weights_kl_reg<NE>(eta, beta, lw, E, h, v);                                  // :256-258
-    } else {
-        updated = false;                                                                  // :260
-        kl = -1.f; eta = -1.f;
-    }
+    auto kl_at = [&](float e) __attribute__((always_inline)) { return weights_kl_reg<NE>(e, beta, lw, E, h, v); };
+    weights_bisect(bound, kl_at, kl, eta, updated);
 #pragma unroll
     for (int e = 0; e < NE; ++e)
         if (h[e]) nl[t + 64 * e] = v[e];                                                  // hand the result to the LDS image
@@ -280,26 +290,8 @@ __global__ __launch_bounds__(64) void update_weights_kernel(int mode, int K, flo
         } else if (K <= 1024) {
             weights_search_reg<16>(K, beta, bound, lw, E, nl, kl, eta, updated);
         } else {
-            float lb = -45.f, ub = 45.f;                                                  // :276-277
-            float log_eta = 0.5f * (ub + lb);
-            bool ub_ok = false;
-            for (int it = 0; it < 50; ++it) {                                             // :232
-                eta = expf(log_eta);
-                if (fabsf(expf(ub) - expf(lb)) < 1e-1f) break;                            // :234-236
-                kl = weights_kl(eta, beta, lw, E, nl, K);                                 // :238
-                if (fabsf(bound - kl) < 1e-1f * bound) { lb = ub; break; }                // :240-243
-                if (bound > kl) { ub = log_eta; ub_ok = true; } else { lb = log_eta; }    // :245-249
-                log_eta = 0.5f * (ub + lb);
-            }
-            if (lb == ub) {
-                // :252-253 keep the last evaluated weights
-            } else if (ub_ok) {
-                eta = expf(ub);
-                kl = weights_kl(eta, beta, lw, E, nl, K);                                 // :256-258
-            } else {
-                updated = false;                                                          // :260
-                kl = -1.f; eta = -1.f;
-            }
+            auto kl_at = [&](float e) __attribute__((always_inline)) { return weights_kl(e, beta, lw, E, nl, K); };
+            weights_bisect(bound, kl_at, kl, eta, updated);
         }
     }
     if (!updated) {
