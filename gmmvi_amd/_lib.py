@@ -196,6 +196,7 @@ _PROTOS = {
     "gmmvi_autodiff_probe_vector": (_i, [_i, _p, _i, _i, _i, _p, _f, _i, C.POINTER(_f), _p]),
     "gmmvi_autodiff_probe_nodes": (_i, [_i, _p, _i, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
     "gmmvi_autodiff_probe_nodes_inputs": (_i, [_i, _p, _i, _i, _i, _i, _i, C.POINTER(_f), _p]),
+    "gmmvi_autodiff_probe_affine": (_i, [_p] + [_i] * 14 + [_p, C.POINTER(_f), _p]),
     "gmmvi_custom_target_check_data": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_plan": (_i, [_i, C.c_int64, _i, C.POINTER(_i), C.POINTER(_i)]),
@@ -212,6 +213,7 @@ _PROTOS = {
     "gmmvi_tape_probe_vector": (_i, [_i, _p, _i, _i, _i, _p, _f, C.POINTER(_f), _p, C.POINTER(_i)]),
     "gmmvi_tape_probe_nodes": (_i, [_i, _p, _i, _i, _i, _i, _i, C.POINTER(_f), _p, C.POINTER(_i)]),
     "gmmvi_tape_probe_nodes_inputs": (_i, [_i, _p, _i, _i, _i, _i, C.POINTER(_f), _p, C.POINTER(_i)]),
+    "gmmvi_tape_probe_affine": (_i, [_p] + [_i] * 13 + [_p, C.POINTER(_f), _p, C.POINTER(_i)]),
     "gmmvi_custom_target_check_data_tape": (_i, [C.c_char_p, C.c_char_p, C.c_char_p, _sz]),
     "gmmvi_custom_target_compile_data_tape": (_i, [_p, C.c_char_p, C.POINTER(_p)]),
     "gmmvi_custom_data_tape_plan": (_i, [_i, C.c_int64, _i, _i, _i, _sz, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),

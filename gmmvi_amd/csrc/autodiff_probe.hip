@@ -167,3 +167,37 @@ extern "C" int gmmvi_autodiff_probe_nodes_inputs(int op, const float* x, int D, 
     for (int j = 0; j < gmmvi_ad::W; ++j) tangents[j] = r.d[j];
     return GMMVI_OK;
 }
+
+// one gmmvi_affine call in the pass seeded at `seed_first`: the array of gmmvi_autodiff_probe_nodes (h[i] = tanh(x[src + i]), every
+// `every`-th entry a constant), or with `inputs` the inputs themselves (h[i] = x[src + i]), or with `floats` the same values as a
+// const float* (the overload that takes constants).  values[j] = out[j], j < m; the output is out[pick], or with pick == -1
+// gmmvi_logsumexp(out, m), which consumes every output; tangents[t] is its derivative by x[seed_first + t].  Distinct (i, j)
+// with distinct indices w + i si + j sj stay the caller's duty, as in the primitive's contract.
+extern "C" int gmmvi_autodiff_probe_affine(const float* x, int D, int w, int si, int sj, int b, int sb, int n, int m, int src, int every,
+                                           int inputs, int floats, int pick, int seed_first, float* values, float* value,
+                                           float* tangents) {
+    constexpr int kMax = 64;
+    if (!x || !values || !value || !tangents || D < 1 || n < 0 || m < 0 || n > kMax || m > kMax || w < 0 || si < 1 || sj < 1 ||
+        src < 0 || every < 0 || seed_first < 0 || src > D - n || pick < -1 || pick >= (m > 0 ? m : 1) ||
+        (n > 0 && m > 0 && (long long)w + (long long)(n - 1) * si + (long long)(m - 1) * sj >= D) ||
+        (b >= 0 && (sb < 1 || (m > 0 && (long long)b + (long long)(m - 1) * sb >= D))))
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_autodiff_probe_affine: needs x, values, value, tangents, D >= 1, 0 <= n <= 64, "
+                                                  "0 <= m <= 64, 0 <= w, 1 <= si, 1 <= sj, 1 <= sb with a bias, 0 <= src, 0 <= every, "
+                                                  "0 <= seed_first, src + n <= D, every weight and bias index below D and "
+                                                  "-1 <= pick < max(m, 1)");
+    const gmmvi_ad::Seed seed{x, seed_first};
+    Dual h[kMax], out[kMax];
+    float hf[kMax];
+    for (int i = 0; i < n; ++i) {
+        hf[i] = inputs ? x[src + i] : ::tanhf(x[src + i]);
+        if (inputs) h[i] = seed[src + i];
+        else h[i] = every > 0 && i % every == every - 1 ? Dual(hf[i]) : tanh(seed[src + i]);
+    }
+    if (floats) gmmvi_affine(seed, w, si, sj, b, sb, (const float*)hf, n, out, m);
+    else gmmvi_affine(seed, w, si, sj, b, sb, (const Dual*)h, n, out, m);
+    for (int j = 0; j < m; ++j) values[j] = out[j].v;
+    const Dual r = m == 0 ? Dual(0.f) : (pick >= 0 ? out[pick] : gmmvi_logsumexp(out, m));
+    *value = r.v;
+    for (int t = 0; t < gmmvi_ad::W; ++t) tangents[t] = r.d[t];
+    return GMMVI_OK;
+}

@@ -30,9 +30,9 @@ static const char* const kDataTapeText =
     ;
 static const char* const kLine = "\n";
 // Goes in front of the user's first line, on that line: a float has no namespace for argument-dependent lookup to search, so
-// the float instantiation of the user's template finds gmmvi_value, the nine functions of custom_target_special.inc and the five
+// the float instantiation of the user's template finds gmmvi_value, the nine functions of custom_target_special.inc and the six
 // of custom_target_vector.inc only if they are declared before the template.  The hand-written mode gets the same line: its float
-// code calls them too.  gmmvi_wdot and gmmvi_logsumexp on an array of duals or nodes are found by argument-dependent lookup at
+// code calls them too.  gmmvi_wdot, gmmvi_logsumexp and gmmvi_affine on an array of duals or nodes are found by argument-dependent lookup at
 // the point of instantiation, in gmmvi_ad and gmmvi_tape: every row of kModes puts kSpecialText, which holds the two value
 // templates they call, in front of the number types, and the number types in front of the kernels that instantiate the user's
 // template with them.
@@ -46,7 +46,8 @@ static const char* const kAutodiffPrelude =
     "__host__ __device__ inline float gmmvi_sqdist(const float*, int, const float*, int); "
     "__host__ __device__ inline float gmmvi_sumsq(const float*, int, int, float); "
     "__host__ __device__ inline float gmmvi_wdot(const float*, int, const float*, int); "
-    "__host__ __device__ inline float gmmvi_logsumexp(const float*, int); ";
+    "__host__ __device__ inline float gmmvi_logsumexp(const float*, int); "
+    "__host__ __device__ inline void gmmvi_affine(const float*, int, int, int, int, int, const float*, int, float*, int); ";
 #define GMMVI_STR2(x) #x
 #define GMMVI_STR(x) GMMVI_STR2(x)
 
@@ -173,7 +174,9 @@ int compile_source(const char* source, Mode mode, const char* arch, std::vector<
     for (const char* define : row.defines)
         if (define) opts.push_back(define);
     // the node-array record (custom_target_tape.inc): its overloads and its branch of the sweep only where the text names them
-    if (strstr(source, "gmmvi_wdot") || strstr(source, "gmmvi_logsumexp")) opts.push_back("-DGMMVI_TAPE_NODES=1");
+    const bool affine = strstr(source, "gmmvi_affine") != nullptr;     // its record group: headers of the node-array kind
+    if (affine || strstr(source, "gmmvi_wdot") || strstr(source, "gmmvi_logsumexp")) opts.push_back("-DGMMVI_TAPE_NODES=1");
+    if (affine) opts.push_back("-DGMMVI_TAPE_AFFINE=1");
     r = rt.compile(prog, (int)opts.size(), opts.data());
     size_t n = 0;
     if (rt.log_size(prog, &n) == HIPRTC_SUCCESS && n > 1) {

@@ -244,6 +244,43 @@ GMMVI_AD_FN Dual gmmvi_logsumexp(const Dual* a, int n) {
     return r;
 }
 
+// ---- gmmvi_affine: out[j] = (sum over i of h[i] * x[w + i * si + j * sj]) + x[b + j * sb], j < m (custom_target_vector.inc has
+// the value).  One pass over n * m.  Tangent t of out[j]: the sum over i of x[..] * h[i].d[t] by fmaf, i ascending; then h[i].v
+// where the seeded input x[x.first + t] is the weight (i, j), which at most one i is (the contract: distinct (i, j) have distinct
+// indices); then 1 where it is the bias of j.  The second overload takes constants for h, and only the last two terms are left.
+// n <= 0: out[j] is the bias, an input, or the constant 0.
+GMMVI_AD_FN void gmmvi_affine(const Seed& x, int w, int si, int sj, int b, int sb, const Dual* h, int n, Dual* out, int m) {
+    for (int o = 0; o < m; ++o) {
+        if (n <= 0) { out[o] = b < 0 ? Dual(0.f) : x[b + o * sb]; continue; }
+        Dual r(::gmmvi_vector::affine_out(x.x, w, si, sj, b, sb, ValueAt{h}, n, o));
+        float own[W];                                                   // h[i].v where tangent t is weight (i, o)'s
+        GMMVI_AD_EACH own[j] = 0.f;
+        for (int i = 0; i < n; ++i) {
+            const int at = w + i * si + o * sj;
+            const float xi = x.x[at];
+            GMMVI_AD_EACH r.d[j] = ::fmaf(xi, h[i].d[j], r.d[j]);
+            const int t = at - x.first;
+            if (t >= 0 && t < W) { GMMVI_AD_EACH own[j] = j == t ? h[i].v : own[j]; }
+        }
+        const int tb = b < 0 ? -1 : b + o * sb - x.first;
+        GMMVI_AD_EACH r.d[j] = (r.d[j] + own[j]) + (j == tb ? 1.f : 0.f);
+        out[o] = r;
+    }
+}
+GMMVI_AD_FN void gmmvi_affine(const Seed& x, int w, int si, int sj, int b, int sb, const float* h, int n, Dual* out, int m) {
+    for (int o = 0; o < m; ++o) {
+        if (n <= 0) { out[o] = b < 0 ? Dual(0.f) : x[b + o * sb]; continue; }
+        Dual r(::gmmvi_vector::affine_out(x.x, w, si, sj, b, sb, ::gmmvi_vector::FloatAt{h}, n, o));
+        for (int i = 0; i < n; ++i) {
+            const int t = w + i * si + o * sj - x.first;
+            if (t >= 0 && t < W) { GMMVI_AD_EACH r.d[j] = j == t ? h[i] : r.d[j]; }
+        }
+        const int tb = b < 0 ? -1 : b + o * sb - x.first;
+        GMMVI_AD_EACH r.d[j] += j == tb ? 1.f : 0.f;
+        out[o] = r;
+    }
+}
+
 }  // namespace gmmvi_ad
 
 // (csrc/custom_target.hip declares this one in front of the user's text as well: the user's float instantiation needs it there)

@@ -11,7 +11,8 @@ R"GMMVI_TAPE(
 // and takes no part in the sweep).  ia <= -2 marks a vector record, the one node of a gmmvi_dot, gmmvi_sqdist or gmmvi_sumsq
 // call on the inputs (custom_target_vector.inc): ia = -2 - (4 n + kind), ib = first, and {pa, pb} hold the 64-bit address of
 // c, or the bits of center in pa.  Kind 3 is the node-array record of gmmvi_wdot and gmmvi_logsumexp, a header behind
-// ceil(n / 2) payload slots ("primitives on arrays of nodes", below).  Record r of lane l lies at rec[r * stride + l], its
+// ceil(n / 2) payload slots ("primitives on arrays of nodes", below), and of gmmvi_affine, m headers behind one payload and two
+// descriptor slots ("gmmvi_affine", below).  Record r of lane l lies at rec[r * stride + l], its
 // adjoint at adj[r * stride + l]: on the device stride = 64, a wave's record r is 1 KiB of consecutive memory and every access
 // below is an ordinary per-lane vector load or store; on the host (csrc/tape_probe.hip) stride = 1 and l = 0.
 // The partial derivatives and the tie rules are those of the forward mode (custom_target_autodiff.inc): fabs has partial 0 at
@@ -288,6 +289,50 @@ GMMVI_TAPE_FN Var gmmvi_logsumexp(const Var* a, int n) {
 }
 #endif
 
+// ---- gmmvi_affine: out[j] = (sum over i of h[i] * x[w + i * si + j * sj]) + x[b + j * sb], j < m, a whole layer as one record
+// group of ceil(n / 2) + 2 + m slots: the payload of gmmvi_wdot (the ids and the bits of h, once for all m outputs; a constant
+// entry keeps its negative id, and every entry of the const float* overload is one), two descriptor slots {w, si, sj, b} and
+// {sb, m, 0, 0}, then m headers {-2 - (4 n + 3), j, 2, 0}: node-array records with operation 2, header j the node of out[j].  No
+// Var refers to a payload or descriptor slot.  The sweep (sweep_vector, below) enters the group at the first header it meets
+// walking backwards and leaves it behind the payload: one visit handles every output.  n <= 0: out[j] is the input x[b + j * sb]
+// itself, or the constant 0; m <= 0 writes nothing; neither makes a record.
+// GMMVI_TAPE_AFFINE: csrc/custom_compile.hip defines it, and GMMVI_TAPE_NODES with it, where the user's text names gmmvi_affine.
+#ifdef GMMVI_TAPE_AFFINE
+#ifndef GMMVI_TAPE_NODES
+#error "GMMVI_TAPE_AFFINE needs GMMVI_TAPE_NODES: its headers are node-array records"
+#endif
+struct IdAt {
+    const Var* p;
+    GMMVI_TAPE_FN int operator()(int i) const { return p[i].id; }
+};
+struct ConstantId {
+    GMMVI_TAPE_FN int operator()(int) const { return -1; }
+};
+template <class At, class Id>
+GMMVI_TAPE_FN void affine(const Input& x, int w, int si, int sj, int b, int sb, At h, Id id, int n, Var* out, int m) {
+    if (m <= 0) return;
+    if (n <= 0) {
+        for (int j = 0; j < m; ++j) out[j] = b < 0 ? Var(0.f) : x[b + j * sb];
+        return;
+    }
+    for (int i = 0; i < n; i += 2) {
+        const bool two = i + 1 < n;
+        push_bits(id(i), two ? id(i + 1) : -1, float_bits(h(i)), two ? float_bits(h(i + 1)) : 0);
+    }
+    push_bits(w, si, sj, b);
+    push_bits(sb, m, 0, 0);
+    for (int j = 0; j < m; ++j)
+        out[j] = Var(::gmmvi_vector::affine_out(x.x, w, si, sj, b, sb, h, n, j),
+                     push_vector(::gmmvi_vector::NODES, j, n, ::gmmvi_vector::AFFINE, 0));
+}
+GMMVI_TAPE_FN void gmmvi_affine(const Input& x, int w, int si, int sj, int b, int sb, const Var* h, int n, Var* out, int m) {
+    affine(x, w, si, sj, b, sb, ValueAt{h}, IdAt{h}, n, out, m);
+}
+GMMVI_TAPE_FN void gmmvi_affine(const Input& x, int w, int si, int sj, int b, int sb, const float* h, int n, Var* out, int m) {
+    affine(x, w, si, sj, b, sb, ::gmmvi_vector::FloatAt{h}, ConstantId{}, n, out, m);
+}
+#endif
+
 // The vector record v at record index r with adjoint w: adds w * d node / d x[first + i] into g[(first + i) * g_stride], i
 // ascending; a node-array record also adds w * d node / d entry i into the adjoint of every entry that is not a constant, from
 // its payload in the slots below r.  x: the lane's inputs.  -> the slots the record spans, which the sweep steps back over.
@@ -297,6 +342,38 @@ GMMVI_TAPE_FN int sweep_vector(const Rec4& v, float w, int r, int D, RecPtr rp, 
 #ifdef GMMVI_TAPE_NODES
     if (kind == ::gmmvi_vector::NODES) {
         const int slots = (n + 1) >> 1;
+#ifdef GMMVI_TAPE_AFFINE
+        // Header j = v.y of a gmmvi_affine group, the first header of the group the lane meets: a later record consumed the
+        // outputs (then j = m - 1), or the function's output is out[j] itself.  Every consumer of out[0 .. j] has been swept, so
+        // the adjoints a_0 .. a_j of headers 0 .. j are final (a header above j has no swept consumer: its adjoint is 0 and it is
+        // left out).  Entry i, ascending, reads its payload once; jj ascending inside it: h[i].v a_jj goes to the gradient of weight
+        // (i, jj), and the sum over jj of x[weight (i, jj)] a_jj, by fmaf from 0, goes once to the entry's adjoint.  Then a_jj to
+        // the gradient of bias jj, jj ascending.  The whole group is stepped over: no other header of it is visited.
+        if (v.z == ::gmmvi_vector::AFFINE) {
+            const int j = v.y, group = r - j - 2 - slots;               // the group's first slot
+            const Rec4 lay = rp[(size_t)(group + slots) * stride];       // {w, si, sj, b}
+            const int sb = rp[(size_t)(group + slots + 1) * stride].x;
+            const AdjPtr a = ap + (size_t)(group + slots + 2) * stride;  // a[jj * stride]: the adjoint of out[jj]
+            for (int i = 0; i < n; ++i) {
+                const Rec4 e = rp[(size_t)(group + (i >> 1)) * stride];
+                const int id = i & 1 ? e.y : e.x;
+                const float hv = bits_float(i & 1 ? e.w : e.z);
+                float d = 0.f;
+                for (int jj = 0; jj <= j; ++jj) {
+                    const int at = lay.x + i * lay.y + jj * lay.z;
+                    const float ajj = a[(size_t)jj * stride];
+                    g[(size_t)at * g_stride] += hv * ajj;
+                    d = ::fmaf(x[at], ajj, d);
+                }
+                if (id >= 0) {
+                    if (id < D) g[(size_t)id * g_stride] += d; else ap[(size_t)(id - D) * stride] += d;
+                }
+            }
+            if (lay.w >= 0)
+                for (int jj = 0; jj <= j; ++jj) g[(size_t)(lay.w + jj * sb) * g_stride] += a[(size_t)jj * stride];
+            return j + 1 + 2 + slots;
+        }
+#endif
         const bool wdot = v.z == ::gmmvi_vector::WDOT;
         for (int i = 0; i < n; ++i) {
             const Rec4 e = rp[(size_t)(r - slots + (i >> 1)) * stride];

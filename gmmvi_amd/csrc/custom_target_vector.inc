@@ -20,6 +20,13 @@ R"GMMVI_VECTOR(
 // types call: gmmvi_wdot in the order above, so that on floats it has the bits of gmmvi_dot; gmmvi_logsumexp as m + logf(s) with
 // m the maximum by fmaxf, i ascending from -inf, and s the sum of expf(a[i] - m) in four partial sums by plain adds, merged as
 // above.  m == -inf (n <= 0, every entry -inf; fmaxf drops NaNs, so an array of NaNs as well) gives -inf and no partials.
+//
+// A whole affine layer is one call, with strides:
+//     gmmvi_affine(x, w, si, sj, b, sb, h, n, out, m)
+//         out[j] = (sum over i < n of h[i] * x[w + i * si + j * sj]) + x[b + j * sb], j < m; b < 0: no bias term
+// h a const T* or a const float*, out a T*.  The sum of every out[j] comes from affine_value below in the order above (with
+// si == 1 it is wdot_value on x + w + j * sj, bit for bit); the bias is one plain add behind it.  n <= 0: out[j] is x[b + j * sb]
+// itself, or 0 without a bias.  m <= 0 writes nothing.
 namespace gmmvi_vector {
 
 enum Kind { DOT = 0, SQDIST = 1, SUMSQ = 2 };                      // the order of _lib.VECTOR_OPS, and the kind of a tape record
@@ -73,6 +80,7 @@ __host__ __device__ inline float sumsq_value(const float* x, int n, float center
 }
 
 enum NodeOp { WDOT = 0, LOGSUMEXP = 1 };                           // the order of _lib.NODE_OPS, and z of a node-array record's header
+constexpr int AFFINE = 2;                                          // z of the headers of a gmmvi_affine record group
 constexpr int NODES = 3;                                           // the kind of the tape's node-array record
 
 struct FloatAt {                                                   // the accessor of a float array
@@ -95,6 +103,30 @@ __host__ __device__ inline float wdot_value(const float* x, At h, int n) {
     if (i + 1 < n) s1 = ::fmaf(h(i + 1), x[i + 1], s1);
     if (i + 2 < n) s2 = ::fmaf(h(i + 2), x[i + 2], s2);
     return (s0 + s1) + (s2 + s3);
+}
+
+// wdot_value with the elements of x `si` apart: x is &x[w + j * sj] of the caller.  All three number types take the sum of
+// gmmvi_affine from here.
+template <class At>
+__host__ __device__ inline float affine_value(const float* x, int si, At h, int n) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int i = 0;
+    for (; i + 4 <= n; i += 4) {
+        s0 = ::fmaf(h(i), x[i * si], s0);
+        s1 = ::fmaf(h(i + 1), x[(i + 1) * si], s1);
+        s2 = ::fmaf(h(i + 2), x[(i + 2) * si], s2);
+        s3 = ::fmaf(h(i + 3), x[(i + 3) * si], s3);
+    }
+    if (i < n) s0 = ::fmaf(h(i), x[i * si], s0);
+    if (i + 1 < n) s1 = ::fmaf(h(i + 1), x[(i + 1) * si], s1);
+    if (i + 2 < n) s2 = ::fmaf(h(i + 2), x[(i + 2) * si], s2);
+    return (s0 + s1) + (s2 + s3);
+}
+// out[j] of gmmvi_affine for n > 0: the sum, then the bias by one plain add
+template <class At>
+__host__ __device__ inline float affine_out(const float* x, int w, int si, int sj, int b, int sb, At h, int n, int j) {
+    const float s = affine_value(x + w + j * sj, si, h, n);
+    return b < 0 ? s : s + x[b + j * sb];
 }
 
 // -> m + logf(s); m and s go back to the caller for the partials.  m == -inf: -> -inf, s = 0, and there are no partials.
@@ -131,6 +163,13 @@ __host__ __device__ inline float gmmvi_wdot(const float* x, int first, const flo
 __host__ __device__ inline float gmmvi_logsumexp(const float* a, int n) {
     float m, s;
     return gmmvi_vector::logsumexp_value(gmmvi_vector::FloatAt{a}, n, m, s);
+}
+__host__ __device__ inline void gmmvi_affine(const float* x, int w, int si, int sj, int b, int sb, const float* h, int n, float* out,
+                                             int m) {
+    for (int j = 0; j < m; ++j) {
+        if (n <= 0) out[j] = b < 0 ? 0.f : x[b + j * sb];
+        else out[j] = gmmvi_vector::affine_out(x, w, si, sj, b, sb, gmmvi_vector::FloatAt{h}, n, j);
+    }
 }
 __host__ __device__ inline float gmmvi_dot(const float* x, int first, const float* c, int n) {
     return gmmvi_vector::dot_value(x + first, c, n);

@@ -6,6 +6,7 @@
 
 #define GMMVI_TAPE_NO_KERNELS
 #define GMMVI_TAPE_NODES 1                                       // the overloads and the sweep of the node-array record
+#define GMMVI_TAPE_AFFINE 1                                      // gmmvi_affine and its branch of that sweep
 #include "build/custom_target_special_text.inc"
 #include "build/custom_target_tape_text.inc"
 
@@ -208,6 +209,46 @@ extern "C" int gmmvi_tape_probe_nodes_inputs(int op, const float* x, int D, int 
     const Var r = op == gmmvi_vector::WDOT ? gmmvi_wdot(in, first, h, n) : gmmvi_logsumexp(h, n);
     *value = r.v;
     *records = gmmvi_tape::count();
+    for (int i = 0; i < D; ++i) grad[i] = 0.f;
+    gmmvi_tape::sweep(r, D, (gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, x, grad, 1);
+    return GMMVI_OK;
+}
+
+// one gmmvi_affine call on a tape: the arguments, the array and the output of gmmvi_autodiff_probe_affine (an entry that is not a
+// constant is one tanh record; with `inputs` or `floats` the entries make no record).  values[j] = out[j]; *records is the lane's
+// count behind the gmmvi_affine call, in front of the gmmvi_logsumexp of pick == -1; grad [D] is what gmmvi_tape::sweep leaves at
+// stride 1, entering the group at header `pick`, or at header m - 1 from the record of the gmmvi_logsumexp
+extern "C" int gmmvi_tape_probe_affine(const float* x, int D, int w, int si, int sj, int b, int sb, int n, int m, int src, int every,
+                                       int inputs, int floats, int pick, float* values, float* value, float* grad, int* records) {
+    constexpr int kMax = 64;
+    if (!x || !values || !value || !grad || !records || D < 1 || n < 0 || m < 0 || n > kMax || m > kMax || w < 0 || si < 1 || sj < 1 ||
+        src < 0 || every < 0 || src > D - n || pick < -1 || pick >= (m > 0 ? m : 1) ||
+        (n > 0 && m > 0 && (long long)w + (long long)(n - 1) * si + (long long)(m - 1) * sj >= D) ||
+        (b >= 0 && (sb < 1 || (m > 0 && (long long)b + (long long)(m - 1) * sb >= D))))
+        return gmmvi_fail(nullptr, GMMVI_ERR_ARG, "gmmvi_tape_probe_affine: needs x, values, value, grad, records, D >= 1, 0 <= n <= 64, "
+                                                  "0 <= m <= 64, 0 <= w, 1 <= si, 1 <= sj, 1 <= sb with a bias, 0 <= src, 0 <= every, "
+                                                  "src + n <= D, every weight and bias index below D and -1 <= pick < max(m, 1)");
+    // a record per entry, the group's payload, descriptors and headers, the gmmvi_logsumexp of the outputs
+    constexpr int kCap = kMax + (kMax / 2 + 2 + kMax) + (kMax / 2 + 1);
+    gmmvi_tape::Rec4 rec[kCap] = {};
+    float adj[kCap] = {};
+    gmmvi_tape::tape() = gmmvi_tape::Tape{(gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, kCap, D};
+    gmmvi_tape::count() = 0;
+    const gmmvi_tape::Input in{x};
+    Var h[kMax], out[kMax];
+    float hf[kMax];
+    for (int i = 0; i < n; ++i) {
+        hf[i] = inputs ? x[src + i] : ::tanhf(x[src + i]);
+        if (floats) continue;
+        if (inputs) h[i] = in[src + i];
+        else h[i] = every > 0 && i % every == every - 1 ? Var(hf[i]) : tanh(in[src + i]);
+    }
+    if (floats) gmmvi_affine(in, w, si, sj, b, sb, (const float*)hf, n, out, m);
+    else gmmvi_affine(in, w, si, sj, b, sb, (const Var*)h, n, out, m);
+    *records = gmmvi_tape::count();
+    for (int j = 0; j < m; ++j) values[j] = out[j].v;
+    const Var r = m == 0 ? Var(0.f) : (pick >= 0 ? out[pick] : gmmvi_logsumexp(out, m));
+    *value = r.v;
     for (int i = 0; i < D; ++i) grad[i] = 0.f;
     gmmvi_tape::sweep(r, D, (gmmvi_tape::RecPtr)rec, (gmmvi_tape::AdjPtr)adj, 1, x, grad, 1);
     return GMMVI_OK;

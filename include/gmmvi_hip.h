@@ -426,6 +426,23 @@ int gmmvi_target_custom(gmmvi_ctx* ctx, const gmmvi_custom_target* target, int D
  * Forward mode: tangent j of gmmvi_wdot is the sum over i of x[first + i] * h[i].d[j], by fmaf, i ascending, plus h[k].v for
  * k = x.first + j - first where 0 <= k < n; tangent j of gmmvi_logsumexp is the sum over i of p_i * a[i].d[j], by fmaf.  One
  * pass over n per call.  Tape modes: one node-array record per call, 1 + ceil(n / 2) slots (below).
+ * A whole affine layer, a matrix of inputs times an array of T plus a bias, is one call with strides:
+ *   - gmmvi_affine(X x, int w, int si, int sj, int b, int sb, const T* h, int n, T* out, int m):
+ *         out[j] = (sum over i < n of h[i] * x[w + i * si + j * sj]) + x[b + j * sb]      for j < m.
+ * b < 0: no bias term.  A second overload takes const float* h, constants, for example the features of a data row in the first
+ * layer; in float code (value calls, the hand-written mode) the two coincide.  out must not alias h.  si >= 1, sj >= 1 (and
+ * sb >= 1 with a bias), every index inside [0, D), and distinct (i, j) giving distinct indices are the caller's duty.  Blocks
+ * [weights | bias] per unit are si = 1, sj = n + 1, b = w + n, sb = n + 1; W [in, out] row-major and then b [out], the layout of
+ * gmmvi_target_bnn below, is si = m, sj = 1, b = w + n * m, sb = 1.  m <= 0 writes nothing; n <= 0: out[j] is the input
+ * x[b + j * sb] itself (derivative 1), or the constant 0 without a bias; neither makes a record.  Entries of h may be constants.
+ * The value: the sum in the order of gmmvi_wdot (four partial sums, fmaf(h[i].value, x[..], s), element i into partial i mod 4,
+ * (s0 + s1) + (s2 + s3)), then the bias by one plain add, from one function for all three number types: a value call and a
+ * gradient call agree bit for bit, and with si == 1 out[j] has the bits of gmmvi_wdot(x, w + j * sj, h, n) + x[b + j * sb].
+ * There is no lifetime rule for h or out.  A const float* in the place of x does not compile in the gradient modes.
+ * Forward mode: one pass over n * m; tangent t of out[j] is the sum over i of x[w + i * si + j * sj] * h[i].d[t] by fmaf, i
+ * ascending, then h[i].v where the seeded input x[x.first + t] is the weight (i, j), then 1 where it is the bias of j.  Tape
+ * modes: one record group of ceil(n / 2) + 2 + m slots per call (below), where m gmmvi_wdot calls and m adds take
+ * m (2 + ceil(n / 2)).
  * The gradient takes ceil(D / W) passes of the dual instantiation, W = GMMVI_CUSTOM_AUTODIFF_TANGENTS, pass `first` writing
  * grad[first + j] for first + j < D; the value is that of the first pass.  That is ceil(D / W) * (1 + W) value evaluations per
  * sample, so a gradient call through such a handle is capped at GMMVI_CUSTOM_AUTODIFF_MAX_DIM; a value call is not. */
@@ -466,6 +483,16 @@ int gmmvi_autodiff_probe_nodes(int op, const float* x, int D, int first, int n, 
  * gmmvi_logsumexp are then its partials p_i bit for bit.  The same arguments are GMMVI_ERR_ARG. */
 int gmmvi_autodiff_probe_nodes_inputs(int op, const float* x, int D, int first, int n, int src, int seed_first, float* value,
                                       float* tangents);
+/* One gmmvi_affine(x, w, si, sj, b, sb, h, n, out, m) in the pass seeded at seed_first.  The array is that of
+ * gmmvi_autodiff_probe_nodes (h[i] = tanh(x[src + i]), every `every`-th entry a constant); inputs != 0: h[i] = x[src + i], the
+ * inputs themselves; floats != 0: the same values as a const float*, the overload that takes constants.  values[m] receives
+ * out[0 .. m).  The output is out[pick] for pick >= 0 and gmmvi_logsumexp(out, m), which consumes every output, for pick == -1
+ * (the constant 0 for m == 0): *value and tangents[GMMVI_CUSTOM_AUTODIFF_TANGENTS] are its value and derivatives by
+ * x[seed_first + t].  A NULL array, D < 1, n or m outside [0, 64], si < 1, sj < 1, sb < 1 with a bias, a negative w, src, every
+ * or seed_first, src + n > D, a weight or bias index outside [0, D), or pick outside [-1, max(m, 1)): GMMVI_ERR_ARG.  Distinct
+ * (i, j) with distinct indices stay the caller's duty. */
+int gmmvi_autodiff_probe_affine(const float* x, int D, int w, int si, int sj, int b, int sb, int n, int m, int src, int every,
+                                int inputs, int floats, int pick, int seed_first, float* values, float* value, float* tangents);
 
 /* ---- user-defined targets summed over a data set --------------------------------------------------------------------------------
  * Posteriors of the shape  log p(x) = log prior(x) + sum over the data rows r of log p(data_r | x):  the source defines one
@@ -584,6 +611,20 @@ int gmmvi_target_custom_data_own_batches(gmmvi_ctx* ctx, const gmmvi_custom_targ
  * The overloads on tape nodes and this branch of the sweep are compiled only into a text that names gmmvi_wdot or gmmvi_logsumexp
  * (the library searches the source for the two names and defines GMMVI_TAPE_NODES): the kernels of every other source are what
  * they were without the two primitives.  A text that builds the name by token pasting therefore does not compile on the tape.
+ * gmmvi_affine makes one record GROUP of ceil(n / 2) + 2 + m slots: the payload of gmmvi_wdot (the ids and the bits of h, once
+ * for all m outputs; every entry of the const float* overload is a constant), two descriptor slots {w, si, sj, b} and
+ * {sb, m, 0, 0}, then m headers {-2 - (4 n + 3), j, 2, 0}: the node-array kind with operation 2.  out[j] is the node of header
+ * j; no Var refers to a payload or descriptor slot; beyond the capacity nothing is stored and the count advances slot by slot.
+ * The sweep, walking backwards, meets some header j of the group first: header m - 1 where a later record consumed the outputs,
+ * any j where the function's output is out[j] (records made after the output are never visited).  The adjoints a_0 .. a_j of
+ * out[0 .. j] are final by then, and this one visit handles them all, in one fixed order: entry i ascending reads its payload
+ * once and, jj ascending from 0 to j, adds h[i].v a_jj to the gradient of weight (i, jj) and gathers the sum over jj of
+ * x[w + i si + jj sj] a_jj by fmaf from 0, which it adds once to the entry's adjoint (the gradient entry where the entry is an
+ * input, nothing for a constant); then a_jj goes to the gradient of bias jj, jj ascending.  The sweep then steps back over
+ * j + 1 + 2 + ceil(n / 2) slots: no other header of the group is visited.  No atomics: the same inputs give the same bits.
+ * The overloads and this branch are compiled only into a text that names gmmvi_affine (GMMVI_TAPE_AFFINE, with which the library
+ * defines GMMVI_TAPE_NODES too): the kernels of every other source, those that call gmmvi_wdot or gmmvi_logsumexp included, are
+ * what they were.
  * Kernels: one lane is one sample, one wave per workgroup.  The lane records the user's function (every store guarded by the
  * capacity; beyond it the value stays right and the count keeps counting), then, in the same launch, seeds the output's adjoint
  * with 1 and walks its own records from the output back to the first.  Adjoints of inputs add up in the lane's own row of
@@ -648,6 +689,14 @@ int gmmvi_tape_probe_nodes(int op, const float* x, int D, int first, int n, int 
 /* The same call on an array whose entries are the input nodes themselves, h[i] = x[src + i] (they make no record, so *records
  * is 1 + ceil(n / 2) or 0), which may be -inf: the gradient of gmmvi_logsumexp is then its partials p_i bit for bit. */
 int gmmvi_tape_probe_nodes_inputs(int op, const float* x, int D, int first, int n, int src, float* value, float* grad, int* records);
+/* One gmmvi_affine call on a host tape: the arguments, the array and the output of gmmvi_autodiff_probe_affine (an entry that
+ * is neither a constant, nor an input, nor a float is one tanh record).  values[m]: out[0 .. m); *records: the lane's count
+ * behind the gmmvi_affine call, the entries' records plus ceil(n / 2) + 2 + m (0 more for n == 0 or m == 0), in front of the
+ * gmmvi_logsumexp of pick == -1; *value and grad[D]: the output and what the sweep of the tape modes leaves from it with adjoint
+ * 1, entering the group at header pick, or at header m - 1 from the record of the gmmvi_logsumexp.  The same arguments are
+ * GMMVI_ERR_ARG. */
+int gmmvi_tape_probe_affine(const float* x, int D, int w, int si, int sj, int b, int sb, int n, int m, int src, int every, int inputs,
+                            int floats, int pick, float* values, float* value, float* grad, int* records);
 
 /* ---- targets summed over a data set, differentiated on a tape ------------------------------------------------------------------
  * The source of the data mode, unchanged (gmmvi_user_row and gmmvi_user_prior, templates over the number type; compiled with
